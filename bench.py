@@ -18,8 +18,22 @@ bf16 straight into the worker arenas (the fp32 master stays sharded), whichever 
 on the wire (distributed.py).
 `--workers-per-gpu W` instead fixes W workers per GPU (weak scaling, population W*N).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does what the value needs and no more: it builds the population, warms up, chooses the
+placement (N = 1, below), times the K steps and prints the line (value, ms_per_step, the timed
+steps' own HIP-event roofline, config, device, native). Everything else described below — CPU
+baselines, the first-allocation / device-copy / stream-ceiling figures, kernel trace, the step with
+broadcast, the `--ops` measurements, and at N > 1 parity, weak companion, other schedules, BASELINE
+configs and the population — runs only with `--full`, after the value, as before.
+`--dump-outputs DIR` writes what the last timed step left its caller (theta and the outer momentum,
+updated in place) to DIR/theta.npy and DIR/momentum.npy in float32 (dump_outputs: large arrays as a
+fixed seeded sample); the inputs are seeded, so two builds given the same arguments can be compared
+array for array. The same arguments include `--full`: at N = 1 a `--full` run takes 5 more steps
+(the first-allocation measurement) before the timed ones, so its dump differs from a plain run's.
+At N > 1 the dump is the gathered theta alone; the momentum stays sharded over the ranks and is not
+written.
 
 `--gpus N` without torchrun (no WORLD_SIZE in the environment) starts its own N rank processes —
 child processes of this one, before anything touches the GPU (no exec) — with RANK / LOCAL_RANK /
@@ -81,6 +95,15 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="after the value, also run every other measurement and check of the line (CPU baselines, "
+                        "the first-allocation / device-copy / stream-ceiling figures, kernel trace, the step with "
+                        "broadcast, --ops, and at N > 1 parity, weak companion, other schedules, BASELINE configs, "
+                        "population); without it the options that tune them have no effect")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last one left a caller of the step with (theta and the "
+                        "outer momentum; arrays over DUMP_SAMPLE_ELEMS elements as a fixed seeded sample) to "
+                        "DIR/<name>.npy in float32")
     p.add_argument("--layout", default="gpt_1p3b")
     p.add_argument("--population", type=int, default=8, help="total workers K (strong scaling)")
     p.add_argument("--workers-per-gpu", type=int, default=None, help="fixed per GPU (weak scaling)")
@@ -159,10 +182,24 @@ def parse(argv=None):
                    help="N>1 population_slerp_7b: the member layout (BASELINE configs[4]: the 7.07B body)")
     p.add_argument("--detail-out", default="auto",
                    help="sidecar JSON with the full record the printed line is a projection of (per-generation "
-                        "pairs, planner layouts, notes); 'auto': gpurun_out/bench_detail_n<N>.json, '' = none")
+                        "pairs, planner layouts, notes), written with --full; 'auto': "
+                        "bench_out/bench_detail_n<N>.json, '' = none")
     a = p.parse_args(argv)
+    if not a.full:
+        # a plain run: set up, warm up, time the steps, print the line; every switchable extra off
+        extras = ("cpu_baseline_seconds", "cpu_sample_elems", "ops", "ops_cpu_seconds", "kernel_trace", "bcast_compare",
+                  "weak_companion", "compare_schedules", "config_companions", "config_layouts", "parity_layout",
+                  "parity_bucket_elems", "population_groups", "population_generations", "population_seed",
+                  "population_reps", "population_layout", "list_same_memory", "extras_deadline", "detail_out")
+        given = ["--" + k.replace("_", "-") for k in extras if getattr(a, k) != p.get_default(k)]
+        if given:
+            print(f"bench.py: {', '.join(given)} only take effect with --full; ignored in this plain run",
+                  file=sys.stderr)
+        a.cpu_baseline_seconds = a.ops_cpu_seconds = 0.0
+        a.kernel_trace = a.bcast_compare = a.weak_companion = a.compare_schedules = a.config_companions = 0
+        a.ops, a.parity_layout, a.detail_out = "none", "", ""
     if a.detail_out == "auto":
-        a.detail_out = os.path.join(ROOT, "gpurun_out", f"bench_detail_n{a.gpus}.json")
+        a.detail_out = os.path.join(ROOT, "bench_out", f"bench_detail_n{a.gpus}.json")
     return a
 
 
@@ -514,6 +551,29 @@ def synth_sharded(theta: torch.Tensor, workers: list[torch.Tensor], rank: int) -
         theta[a:b].copy_(t)
         for w in workers:
             w[a:b].copy_(t + torch.randn(b - a, generator=gw, device=dev) * 1e-3)
+
+
+DUMP_SAMPLE_ELEMS = 1 << 22      # per array: 16 MiB of float32, far inside the 64 MB a dump may take
+
+
+def dump_outputs(directory: str, arrays: dict) -> dict:
+    """`--dump-outputs`: each tensor as DIR/<name>.npy in float32 (fp32 and bf16 both convert
+    exactly). A tensor over DUMP_SAMPLE_ELEMS elements is written as a sample: the elements at
+    DUMP_SAMPLE_ELEMS sorted indices drawn from a CPU generator seeded with the tensor's size, so two
+    builds run with the same arguments write the same elements. Returns the line's record."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    rec = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_SAMPLE_ELEMS:
+            g = torch.Generator().manual_seed(n)
+            idx = torch.randint(0, n, (DUMP_SAMPLE_ELEMS,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(directory, f"{name}.npy"), flat.float().cpu().numpy())
+        rec[name] = {"elements": n, "written": flat.numel()}
+    return rec
 
 
 def native_library_record() -> dict:
@@ -1454,6 +1514,15 @@ def run_sharded(args, comm, rt, json_out, kernels=None, exit_fn=None) -> dict | 
     value = bytes_reduced / (ms_per_step / 1e3) / 1e9
     sched = f"{sync.mode}/{sync.broadcast}"
     wire_main = sync.wire_bytes()
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step left its caller: the new theta (every rank gathers, rank 0 writes)
+        th = sync.gather_theta()[:P]
+        rt.sync()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"theta": th})
+        del th
+        comm.barrier()
 
     out = None
     if rank == 0:
@@ -1490,6 +1559,8 @@ def run_sharded(args, comm, rt, json_out, kernels=None, exit_fn=None) -> dict | 
             "roofline": roofline,
             "device": rt.device_info(), "native": native_library_record(),
         }
+        if dumped:
+            out["dumped_outputs"] = dumped
         # rank 0 times the CPU baseline first (the other ranks wait at the barrier), then every
         # extra runs under the deadline, so neither can be lost to a hang in an extra
         if args.cpu_baseline_seconds > 0:
@@ -1652,9 +1723,9 @@ def main():
         step()
     torch.cuda.synchronize()
     placement = None
-    # the fused step on the first allocation, before any placement search: what the drop-in list
-    # path and any first-allocation user get, reported beside the placed value
-    unplaced_ms = _event_ms(step, 5, 0)
+    # --full: the fused step on the first allocation, before any placement search: what the drop-in
+    # list path and any first-allocation user get, reported beside the placed value
+    unplaced_ms = _event_ms(step, 5, 0) if args.full else None
     if args.place_candidates > 1:
         # once per run, outside the timed region: the operand set goes wherever the step's access
         # pattern runs fastest — `--place-draws` regions of HBM for theta and the workers, the
@@ -1684,6 +1755,13 @@ def main():
     value = bytes_reduced / (ms_per_step / 1e3) / 1e9
     if rank != 0:
         return
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step left its caller: the step updates theta and the momentum in place
+        arrays = {"theta": sync.theta.flat}
+        if sync.state.momentum is not None:
+            arrays["momentum"] = sync.state.momentum
+        dumped = dump_outputs(args.dump_outputs, arrays)
     bg = torch.finfo(tdt).bits // 8
     bw = torch.finfo(wdt).bits // 8
     per_elem = k_local * bw + 2 * bg + (2 * bg if args.momentum else 0)
@@ -1712,7 +1790,17 @@ def main():
         "roofline": roofline,
         "device": rt.device_info(), "native": native_library_record(),
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
+    if placement:
+        roofline["placement"] = _placement_record(placement)
+        if "momentum" in placement:
+            roofline["momentum_placement"] = placement["momentum"]
+    if not args.full:
+        emit_line(out, json_out, args.detail_out)
+        return
 
+    # everything below is --full: measurements and checks beside the value, each a run of its own
     # what a plain device-to-device copy reaches on this device, same process
     src = torch.empty(1 << 29, dtype=torch.float32, device=dev)
     dst = torch.empty_like(src)
@@ -1740,10 +1828,6 @@ def main():
     roofline["unplaced_frac"] = round(algo_bytes / (unplaced_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)
     roofline["unplaced_note"] = ("the fused step (HIP events, 5 launches) on the operands' first allocation, "
                                  "before the placement search; kernel_ms is after it")
-    if placement:
-        roofline["placement"] = _placement_record(placement)
-        if "momentum" in placement:
-            roofline["momentum_placement"] = placement["momentum"]
     if args.kernel_trace > 0:
         try:
             out["kernel_trace"] = kernel_trace(step, args.kernel_trace)

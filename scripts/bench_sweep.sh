@@ -5,7 +5,7 @@ set -u
 OUT=gpurun_out/sweep; mkdir -p $OUT
 run() {  # name, args
   local name=$1; shift
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-baseline-seconds 2 "$@" > $OUT/$name.log 2>&1 \
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --cpu-baseline-seconds 2 "$@" > $OUT/$name.log 2>&1 \
     || { tail -5 $OUT/$name.log; exit 1; }
   tail -1 $OUT/$name.log > $OUT/$name.json
   python3 -c "import json; d=json.load(open('$OUT/$name.json')); r=d['roofline']; print('$name', d['ms_per_step'], d['value'], r['frac'], r.get('frac_of_stream_ceiling'))"

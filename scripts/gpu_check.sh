@@ -13,12 +13,12 @@ stop_if_fatal() {  # $1 = exit status of the previous GPU step
 }
 echo "== smoke"; timeout -k 10 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; s=$?; tail -3 $OUT/smoke.log; stop_if_fatal $s
 echo "== pytest -m gpu"; timeout -k 10 900 python -m pytest tests -q -m gpu ${PYTEST_ARGS:-} > $OUT/pytest_gpu.log 2>&1; s=$?; tail -15 $OUT/pytest_gpu.log; stop_if_fatal $s
-echo "== bench"; timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; s=$?; tail -3 $OUT/bench.log; stop_if_fatal $s
+echo "== bench"; timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; s=$?; tail -3 $OUT/bench.log; stop_if_fatal $s
 if [ "${PROFILE:-1}" = "1" ]; then
   echo "== rocprofv3 kernel trace"
   R=$(pwd)
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
-      -d $R/$OUT/prof -o bench -- python3 $R/bench.py ${BENCH_ARGS:-} \
+      -d $R/$OUT/prof -o bench -- python3 $R/bench.py --full ${BENCH_ARGS:-} \
       > $R/$OUT/prof.log 2>&1); s=$?; tail -3 $OUT/prof.log; stop_if_fatal $s   # the bench command itself
   find $OUT/prof -name "*stats*" | head
 fi

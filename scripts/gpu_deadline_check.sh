@@ -5,11 +5,11 @@
 set -u
 cd "$(dirname "$0")/.."
 OUT=gpurun_out; mkdir -p $OUT
-timeout -k 10 300 python bench.py > $OUT/dl_n1.log 2>&1 || exit $?
+timeout -k 10 300 python bench.py --full > $OUT/dl_n1.log 2>&1 || exit $?
 grep '^{' $OUT/dl_n1.log > $OUT/dl_n1.json
-timeout -k 10 400 python bench.py --gpus 1 --sharded > $OUT/dl_sharded.log 2>&1 || exit $?
+timeout -k 10 400 python bench.py --full --gpus 1 --sharded > $OUT/dl_sharded.log 2>&1 || exit $?
 grep '^{' $OUT/dl_sharded.log > $OUT/dl_sharded.json
-timeout -k 10 200 python bench.py --gpus 1 --sharded --extras-deadline 3 > $OUT/dl_fire.log 2>&1; s=$?
+timeout -k 10 200 python bench.py --full --gpus 1 --sharded --extras-deadline 3 > $OUT/dl_fire.log 2>&1; s=$?
 echo "deadline run exit status $s"
 grep '^{' $OUT/dl_fire.log > $OUT/dl_fire.json || exit 1
 python - <<'EOF'

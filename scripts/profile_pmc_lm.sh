@@ -5,7 +5,7 @@ set -u
 cd "$(dirname "$0")/.."
 R=$(pwd); OUT=$R/gpurun_out/pmc_lm
 mkdir -p $OUT
-ARGS="--layout gpt2_small --steps 1 --warmup 0 --cpu-baseline-seconds 0 --ops-cpu-seconds 0 --bcast-compare 0 --place-candidates 1 --ops lm_population"
+ARGS="--full --layout gpt2_small --steps 1 --warmup 0 --cpu-baseline-seconds 0 --ops-cpu-seconds 0 --bcast-compare 0 --place-candidates 1 --ops lm_population"
 KRE="pair_population"
 for C in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --pmc $C --kernel-include-regex "$KRE" --output-format csv \

@@ -5,7 +5,7 @@ set -u
 cd "$(dirname "$0")/.."
 R=$(pwd); OUT=$R/gpurun_out/pmc_ops
 mkdir -p $OUT
-ARGS="--steps 3 --warmup 1 --cpu-baseline-seconds 0 --ops-cpu-seconds 0 --bcast-compare 0 --place-candidates 1 --ops list_form,configs1_125m,pair_merge,slerp_7b --list-same-memory 0"
+ARGS="--full --steps 3 --warmup 1 --cpu-baseline-seconds 0 --ops-cpu-seconds 0 --bcast-compare 0 --place-candidates 1 --ops list_form,configs1_125m,pair_merge,slerp_7b --list-same-memory 0"
 # counters on the measured kernels only (torch's fill / cast launches are not profiled)
 KRE="outer|pair_kernel|pair_sums|slerp"
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -6,7 +6,7 @@ set -u
 cd "$(dirname "$0")/.."
 R=$(pwd); OUT=$R/gpurun_out/pmc_pop
 mkdir -p $OUT
-ARGS="--layout gpt2_small --steps 1 --warmup 0 --cpu-baseline-seconds 0 --bcast-compare 0 --place-candidates 1 --ops population_7b --population-generations 3 --population-reps 10"
+ARGS="--full --layout gpt2_small --steps 1 --warmup 0 --cpu-baseline-seconds 0 --bcast-compare 0 --place-candidates 1 --ops population_7b --population-generations 3 --population-reps 10"
 # counters on the population passes only (torch's fill launches are not profiled)
 KRE="slerp"
 for C in FETCH_SIZE WRITE_SIZE; do

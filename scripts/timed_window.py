@@ -1,4 +1,5 @@
-"""The timed steps' launches out of a rocprofv3 kernel trace of `python bench.py`: the fused step
+"""The timed steps' launches out of a rocprofv3 kernel trace of `python bench.py --full` (a plain
+run has no first-allocation launches, so its windows sit 5 launches earlier): the fused step
 template at the 1.3B grid, in launch order, is [1 first step + 4 warm-up] [5 first-allocation
 (unplaced) launches] [1 after the placement search] [the --steps timed launches] [2 traced] [the
 step-with-broadcast comparison] [the list_form same-memory arenas]. The whole-trace average mixes

@@ -104,3 +104,43 @@ def test_xgmi_floor():
     assert bench.xgmi_floor_ms(0, 8) is None and bench.xgmi_floor_ms(1 << 30, 1) is None
     w = 7 * int(bench.XGMI_LINK_GBPS * 1e9) // 1000     # 1 ms of 7 links
     assert bench.xgmi_floor_ms(w, 8) == pytest.approx(1.0, rel=1e-6)
+
+
+def test_plain_run_switches_every_extra_off(capsys):
+    """Without --full the options of the extras have no effect (stderr names the ones given); with
+    it they keep their values."""
+    assert bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"]).steps == 7
+    assert capsys.readouterr().err == ""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--ops", "pair_merge", "--kernel-trace", "3"])
+    err = capsys.readouterr().err
+    assert "--ops, --kernel-trace only take effect with --full" in err and "--steps" not in err
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.ops == "none" and a.cpu_baseline_seconds == 0 and a.kernel_trace == 0 and a.bcast_compare == 0
+    assert not (a.weak_companion or a.compare_schedules or a.config_companions or a.parity_layout or a.detail_out)
+    f = bench.parse(["--full", "--ops", "pair_merge", "--kernel-trace", "3"])
+    assert f.full and f.ops == "pair_merge" and f.kernel_trace == 3 and f.cpu_baseline_seconds > 0
+    assert f.weak_companion and f.compare_schedules and f.config_companions and f.parity_layout
+    assert f.detail_out.endswith(os.path.join("bench_out", "bench_detail_n1.json"))
+    assert capsys.readouterr().err == ""
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """Small arrays are written whole, larger ones as the same seeded, sorted sample every time;
+    bf16 is written as float32 exactly."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ELEMS", 1000)
+    small = torch.arange(1000, dtype=torch.float32)
+    big = torch.arange(5001, dtype=torch.float32)
+    half = torch.tensor([1.0, 0.5, -3.140625]).bfloat16()
+    rec = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big, "half": half})
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big})
+    assert rec == {"small": {"elements": 1000, "written": 1000}, "big": {"elements": 5001, "written": 1000},
+                   "half": {"elements": 3, "written": 3}}
+    h = np.load(tmp_path / "a" / "half.npy")
+    assert h.dtype == np.float32 and h.tolist() == [1.0, 0.5, -3.140625]
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == b.dtype == np.float32 and np.array_equal(s, small.numpy())
+    assert b.shape == (1000,) and np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    assert np.all(np.diff(b) >= 0) and len(np.unique(b)) > 500            # sorted indices of a monotone array
+    assert np.isin(b, big.numpy()).all()

@@ -23,7 +23,7 @@ LAYOUTS = {"rehearsal_main": [(64, 33), (257,), (31, 17), (1000,)],
            "rehearsal_c2": [(40, 24), (24,), (333,)],
            "rehearsal_c3": [(128, 9), (77,)],
            "rehearsal_pop": [(300,), (17, 19), (1024,)]}
-ARGS = ["--layout", "rehearsal_main", "--population", "4", "--steps", "2", "--warmup", "1",
+ARGS = ["--full", "--layout", "rehearsal_main", "--population", "4", "--steps", "2", "--warmup", "1",
         "--cpu-baseline-seconds", "0.2", "--cpu-sample-elems", "4096", "--bucket-elems", "2048",
         "--config-layouts", "configs2_125m_fp32=rehearsal_c2:f32,configs3_1p3b_bf16=rehearsal_c3:bf16",
         "--population-layout", "rehearsal_pop", "--population-groups", "2",

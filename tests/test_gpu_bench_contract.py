@@ -29,7 +29,7 @@ def _run(*extra, full=False):
     detail = os.path.join(tempfile.mkdtemp(prefix="edt_bench_"), "detail.json")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR",
                                                            "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--layout", "gpt2_small", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--layout", "gpt2_small", "--steps", "3", "--warmup", "1",
            "--cpu-baseline-seconds", "0.4", "--cpu-sample-elems", str(1 << 18), "--ops-cpu-seconds", "0.2",
            "--detail-out", detail, *extra]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=110)
@@ -76,6 +76,38 @@ def test_single_gpu_line():
     top = kt["kernels"][0]
     assert "outer_kernel<" in top["name"] and top["launches"] == 2, kt
     assert top["mean_ms"] > 0
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the run times the steps and prints the line, no extras (their options are
+    inert); --dump-outputs writes the last step's theta and momentum as float32 .npy, a seeded
+    sample where the array is larger than bench.DUMP_SAMPLE_ELEMS."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR",
+                                                           "MASTER_PORT")}
+    dump = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--layout", "gpt2_small",
+                        "--steps", "4", "--warmup", "1", "--place-candidates", "2", "--ops", "pair_merge",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, env=env, timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert TOP - {"cpu_baseline"} <= set(d) and d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    for key in ("cpu_baseline", "kernel_trace", "step_with_broadcast", "pair_merge", "detail"):
+        assert key not in d, key
+    assert "unplaced_ms" not in d["roofline"] and "stream_ceiling_GBps" not in d["roofline"]
+    P = d["config"]["params"]
+    assert P > bench.DUMP_SAMPLE_ELEMS
+    assert sorted(os.listdir(dump)) == ["momentum.npy", "theta.npy"]
+    for name in ("theta", "momentum"):
+        x = np.load(dump / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == (bench.DUMP_SAMPLE_ELEMS,) and np.isfinite(x).all()
+        assert d["dumped_outputs"][name] == {"elements": P, "written": bench.DUMP_SAMPLE_ELEMS}
+    theta = np.load(dump / "theta.npy")
+    assert abs(float(theta.std()) - 0.02) < 1e-3          # theta ~ N(0, .02^2) moved by steps of ~1e-3
 
 
 def test_multi_gpu_path_line_at_world_1():

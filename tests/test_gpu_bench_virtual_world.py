@@ -24,7 +24,7 @@ LAYOUTS = {"vw_main": [(640, 330), (2570,), (310, 170), (10000,)],
            "vw_c2": [(400, 240), (240,), (3330,)],
            "vw_c3": [(1280, 90), (770,)],
            "vw_pop": [(3000,), (170, 190), (10240,)]}
-ARGS = ["--layout", "vw_main", "--steps", "3", "--warmup", "1", "--kernel-trace", "0",
+ARGS = ["--full", "--layout", "vw_main", "--steps", "3", "--warmup", "1", "--kernel-trace", "0",
         "--cpu-baseline-seconds", "0.2", "--cpu-sample-elems", "4096", "--bucket-elems", "32768",
         "--config-layouts", "configs2_125m_fp32=vw_c2:f32,configs3_1p3b_bf16=vw_c3:bf16",
         "--population-layout", "vw_pop", "--population-groups", "2",
