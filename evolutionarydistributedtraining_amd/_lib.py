@@ -18,6 +18,8 @@ LIB_PATH = os.path.join(PKG_DIR, "libedt_sync.so")
 EDT_F32 = 0
 EDT_BF16 = 1
 EDT_MAX_WORKERS = 64
+EDT_MXFP8 = 0               # edt_qfmt_t: the wire formats of the quantized partial exchange
+EDT_MXFP4 = 1
 EDT_ABI_VERSION = 6         # include/edt_sync.h: the revision these signatures and workspace sizes follow
 
 _DT = {torch.float32: EDT_F32, torch.bfloat16: EDT_BF16}
@@ -42,6 +44,9 @@ SIGNATURES = [
     ("edt_delta_partial", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _P, _I, _P]),
     ("edt_sgd_apply", _I, [_P, _I, _P, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_sgd_apply_sum", _I, [_P, _I, ctypes.POINTER(_P), _I, _P, _I, _U64, _D, _D, _I, _P]),
+    ("edt_q_region_bytes", _U64, [_U64, _I]),
+    ("edt_delta_partial_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _U64, _I, _P, _P, _P]),
+    ("edt_sgd_apply_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_to", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_population", _I, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),

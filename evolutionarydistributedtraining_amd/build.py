@@ -16,8 +16,10 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
-# one shared object from four translation units (DiLoCo, pair merge + lerp, SLERP, ABI misc)
-SOURCES = [os.path.join(CSRC, f) for f in ("edt_outer.hip", "edt_merge.hip", "edt_slerp.hip", "edt_abi.hip")]
+# one shared object from five translation units (DiLoCo, pair merge + lerp, SLERP, ABI misc, the
+# quantized partial exchange)
+SOURCES = [os.path.join(CSRC, f) for f in ("edt_outer.hip", "edt_merge.hip", "edt_slerp.hip", "edt_abi.hip",
+                                           "edt_quant.hip")]
 HEADER = os.path.join(ROOT, "include", "edt_sync.h")
 DEPS = SOURCES + [HEADER, os.path.join(CSRC, "edt_common.h")]
 OUT = os.path.join(PKG_DIR, "libedt_sync.so")

@@ -1,0 +1,371 @@
+// edt_quant.hip — the block-quantized partial exchange of the sharded outer step (the "reduce_q"
+// schedule of distributed.ShardedOuterSync): phase 1 forms each rank's fp32 pseudo-gradient partial
+// (edt_delta_partial's math, bit for bit) and writes it as OCP MX blocks — MXFP8 (E4M3 elements)
+// or MXFP4 (E2M1 elements), 32 elements per E8M0 scale byte — without the fp32 partial ever
+// reaching HBM; phase 2 dequantizes the owned shard's N regions, sums them in rank order
+// (edt_sgd_apply_sum's order) and runs the SGD step. The reference ships checkpoints over a shared
+// disk (EDT_LM/diloco.py:231-235) and has no wire format; this one is defined here and in
+// DESIGN.md §3.
+//
+// Wire format (the definition; tests/quant_reference.py restates it in numpy)
+//   block     32 consecutive elements of a rank's fp32 partial share one E8M0 scale byte (bias 127)
+//   scale     e = floor(log2(amax)) - emax, emax = 8 (E4M3) / 2 (E2M1); byte = clamp(e + 127, 0, 254);
+//             an all-zero block (+-0) stores byte 0
+//   elements  v * 2^-e rounded to nearest-even onto the element grid, saturating at +-448 / +-6
+//             (never NaN); the sign is kept, -0 and values that round to zero included
+//   non-finite  a block holding any NaN or +-Inf stores scale byte 255 and elements of code 0; every
+//             element of it dequantizes to NaN
+//   packing   MXFP8: one byte per element; MXFP4: element 2i in the low nibble, 2i+1 in the high
+//             nibble. A region of R elements (R % 512 == 0) is R*bits/8 payload bytes, then R/32
+//             scale bytes: both start 16-byte aligned
+//   D(q)      elem * 2^e, exact in fp32
+//   fp32 subnormal inputs are outside the bit-exact contract (finite, within one grid step).
+//
+// Mapping: a thread owns 8 consecutive elements (one 16-byte load per bf16 operand, two per fp32
+// operand), so 4 adjacent lanes hold a block: the block amax is a two-step xor butterfly, a wave
+// covers 512 elements = 16 blocks, and sizes are multiples of 512 so every wave is whole. Payload
+// leaves as one 8-byte (MXFP8) or 4-byte (MXFP4) store per lane, contiguous across the wave; the
+// 16 scale bytes of a wave are gathered across lanes into four dwords stored by lanes 0/16/32/48.
+#include "edt_common.h"
+
+namespace {
+
+struct QWorkers {
+    const void* p[EDT_MAX_WORKERS];
+};
+
+struct QPartialArgs {
+    const void* theta;
+    float* residual;         // error feedback (EF): read, added, rewritten
+    uint8_t* packed;         // [region][payload | scales]
+    uint64_t n;
+    uint64_t tiles_per_region;   // region_elems / 512
+    uint64_t region_bytes;
+    uint64_t payload_bytes;      // of one region
+    int K;
+    float kdiv;
+    float kinv;
+    QWorkers w;
+};
+
+// element formats: mantissa bits, smallest normal exponent, exponent bias, largest magnitude, emax
+template <int FMT> struct QFmt;
+template <> struct QFmt<EDT_MXFP8> {
+    static constexpr int MB = 3, EMIN = -6, BIAS = 7, EMAX = 8, BITS = 8;
+    static constexpr float MAXV = 448.f;
+};
+template <> struct QFmt<EDT_MXFP4> {
+    static constexpr int MB = 1, EMIN = 0, BIAS = 1, EMAX = 2, BITS = 4;
+    static constexpr float MAXV = 6.f;
+};
+
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }   // -126 <= e <= 127
+
+// |x| (finite, < 2^(EMAX + 1)) rounded to nearest-even onto the element grid and saturated:
+// adding 2^23 q, q the grid step at |x|, makes the fp32 adder round at q.
+template <int FMT>
+__device__ __forceinline__ float q_round(float a) {
+    using F = QFmt<FMT>;
+    int k = (int)(__float_as_uint(a) >> 23) - 127;
+    k = k < F::EMIN ? F::EMIN : k;
+    const float magic = pow2f(k - F::MB + 23);
+    const float r = (a + magic) - magic;
+    return r > F::MAXV ? F::MAXV : r;
+}
+
+// the magnitude code of a grid value r (q_round's result)
+template <int FMT>
+__device__ __forceinline__ uint32_t q_code(float r) {
+    using F = QFmt<FMT>;
+    if (r < pow2f(F::EMIN)) return (uint32_t)(r * pow2f(F::MB - F::EMIN));       // zero and subnormals
+    return (__float_as_uint(r) >> (23 - F::MB)) - ((uint32_t)(127 - F::BIAS) << F::MB);
+}
+
+// magnitude code -> value
+template <int FMT>
+__device__ __forceinline__ float q_decode(uint32_t c) {
+    using F = QFmt<FMT>;
+    if (FMT == EDT_MXFP8 && c == 0x7fu) return __builtin_nanf("");                  // OCP E4M3's NaN
+    if (c < (1u << F::MB)) return (float)c * pow2f(F::EMIN - F::MB);
+    return __uint_as_float((c + ((uint32_t)(127 - F::BIAS) << F::MB)) << (23 - F::MB));
+}
+
+// Phase 1 for the 8 elements at i (a multiple of 8; the wave's 64 lanes cover 512 consecutive ones).
+template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
+__device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t i) {
+    using F = QFmt<FMT>;
+    constexpr int N = kVec;
+    float g[N], acc[N];
+    ld<GDT, N, (EDT_NT_RMW != 0)>(a.theta, i, g);
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = 0.f;
+    const int K = KC > 0 ? KC : a.K;
+    // edt_delta_partial's body (edt_outer.hip, MODE_PARTIAL): the rounded quotients summed in fp32
+    auto body = [&](int k) {
+        float w[N];
+        ld<WDT, N, nt_worker_loads<WDT, 4>()>(a.w.p[k], i, w);
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = w[j] - g[j];
+        rnd<GDT>(w);
+        if constexpr (DIV) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) w[j] = w[j] / a.kdiv;
+        } else {
+#pragma unroll
+            for (int j = 0; j < N; ++j) w[j] = w[j] * a.kinv;
+        }
+        rnd<GDT>(w);
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc[j] = acc[j] + w[j];
+    };
+    if constexpr (KC > 0) {
+#pragma unroll
+        for (int k = 0; k < KC; ++k) body(k);
+    } else {
+#pragma unroll 4
+        for (int k = 0; k < K; ++k) body(k);
+    }
+    if constexpr (EF) {
+        float r[N];
+        ld<EDT_F32, N>(a.residual, i, r);
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc[j] = acc[j] + r[j];          // p' = p + r
+    }
+    // block amax over the bit patterns of |v| (monotone for finite values; NaN / Inf compare highest)
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint32_t u = __float_as_uint(acc[j]) & 0x7fffffffu;
+        m = u > m ? u : m;
+    }
+    uint32_t o = (uint32_t)__shfl_xor((int)m, 1);
+    m = o > m ? o : m;
+    o = (uint32_t)__shfl_xor((int)m, 2);
+    m = o > m ? o : m;
+    const bool bad = m >= 0x7f800000u;
+    int sb = (int)(m >> 23) - F::EMAX;                   // e + 127
+    sb = sb < 0 ? 0 : sb;
+    if (bad) sb = 255;
+    // v * 2^-e = v * 2^(127 - sb): one exact multiply; back by 2^e as two exact factors, since
+    // 2^-127 (scale byte 0) is no normal fp32
+    const int up = bad ? 0 : 127 - sb;                   // -125 .. 127
+    const float su = pow2f(up);
+    const float d0 = pow2f(up > 64 ? -64 : -up), d1 = pow2f(up > 64 ? 64 - up : 0);
+    uint32_t code[N];
+    float deq[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint32_t sign = __float_as_uint(acc[j]) & 0x80000000u;
+        const float ax = __uint_as_float(__float_as_uint(acc[j]) & 0x7fffffffu) * su;
+        const float r = q_round<FMT>(bad ? 0.f : ax);
+        code[j] = bad ? 0u : (q_code<FMT>(r) | (sign >> (32 - F::BITS)));
+        deq[j] = bad ? __builtin_nanf("") : __uint_as_float(__float_as_uint(r * d0 * d1) | sign);   // D(q)
+    }
+    if constexpr (EF) {
+        float r[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) r[j] = acc[j] - deq[j];          // r = p' - D(q)
+        st<EDT_F32, N, false>(a.residual, i, r);
+    }
+    // addresses: tile = 512 elements = one wave; a region is a whole number of tiles
+    const uint64_t tile = i >> 9;
+    uint64_t reg;
+    if ((tile | a.tiles_per_region) >> 32) reg = tile / a.tiles_per_region;
+    else reg = (uint32_t)tile / (uint32_t)a.tiles_per_region;
+    const uint64_t off = i - reg * (a.tiles_per_region << 9);        // element offset inside the region
+    uint8_t* base = a.packed + reg * a.region_bytes;
+    if constexpr (FMT == EDT_MXFP8) {
+        u32x2 v;
+        v.x = code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24);
+        v.y = code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24);
+        *reinterpret_cast<u32x2*>(base + off) = v;
+    } else {
+        uint32_t v = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) v |= code[j] << (4 * j);
+        *reinterpret_cast<uint32_t*>(base + (off >> 1)) = v;
+    }
+    // the wave's 16 scale bytes: lanes 4b .. 4b+3 hold block b's; each group of 16 lanes gathers
+    // its four into one dword by an or-butterfly, and its first lane stores it
+    const unsigned lane = threadIdx.x & 63u;
+    uint32_t sw = (uint32_t)sb << (8 * ((lane >> 2) & 3u));
+    sw |= (uint32_t)__shfl_xor((int)sw, 4);
+    sw |= (uint32_t)__shfl_xor((int)sw, 8);
+    if ((lane & 15u) == 0) *reinterpret_cast<uint32_t*>(base + a.payload_bytes + (off >> 5)) = sw;
+}
+
+template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
+__global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_kernel(QPartialArgs a) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t nv = a.n / kVec;                      // n % 512 == 0: a wave is in or out as a whole
+    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride)
+        partial_q_elems<GDT, WDT, KC, DIV, FMT, EF>(a, v * kVec);
+}
+
+// ---------------------------------------------------------------------------------------
+// phase 2
+
+struct QRegions {
+    const uint8_t* p[EDT_MAX_WORKERS];
+};
+
+template <int FMT>
+__device__ __forceinline__ void ld_q(const uint8_t* region, uint64_t n, uint64_t i, float (&x)[kVec]) {
+    using F = QFmt<FMT>;
+    uint32_t code[kVec];
+    if constexpr (FMT == EDT_MXFP8) {
+        const u32x2 v = *reinterpret_cast<const u32x2*>(region + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { code[j] = (v.x >> (8 * j)) & 0xffu; code[4 + j] = (v.y >> (8 * j)) & 0xffu; }
+    } else {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(region + (i >> 1));
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) code[j] = (v >> (4 * j)) & 0xfu;
+    }
+    const uint32_t sb = region[n * F::BITS / 8 + (i >> 5)];
+    const int e = (int)sb - 127;                         // elem * 2^e as two exact factors
+    const float f0 = pow2f(e < -64 ? -64 : e), f1 = pow2f(e < -64 ? e + 64 : 0);
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+        const uint32_t sign = (code[j] >> (F::BITS - 1)) << 31;
+        const float mag = q_decode<FMT>(code[j] & ((1u << (F::BITS - 1)) - 1u)) * f0 * f1;
+        x[j] = sb == 255u ? __builtin_nanf("") : __uint_as_float(__float_as_uint(mag) | sign);
+    }
+}
+
+template <int GDT, int FMT>
+__global__ __launch_bounds__(kBlock) void sgd_apply_sum_q_kernel(void* theta, QRegions P, int np, void* mom,
+                                                                 uint64_t n, SgdScalars s) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t nv = n / kVec;
+    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
+        const uint64_t i = v * kVec;
+        float g[kVec], a[kVec], grad[kVec], b_in[kVec];
+        ld<GDT, kVec>(theta, i, g);
+        ld_momentum<GDT, kVec>(mom, i, s, b_in);
+        ld_q<FMT>(P.p[0], n, i, a);
+        for (int r = 1; r < np; ++r) {                  // rank order, as sgd_apply_sum_kernel
+            float x[kVec];
+            ld_q<FMT>(P.p[r], n, i, x);
+#pragma unroll
+            for (int j = 0; j < kVec; ++j) a[j] = a[j] + x[j];
+        }
+        rnd<GDT>(a);
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) grad[j] = -a[j];
+        sgd_update<GDT, kVec>(g, grad, mom, i, s, b_in);
+        st<GDT, kVec>(theta, i, g);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// launch helpers
+
+inline int fmt_bits(int fmt) { return fmt == EDT_MXFP8 ? 8 : fmt == EDT_MXFP4 ? 4 : 0; }
+
+template <int GDT, int WDT, int FMT, bool EF>
+int launch_partial_q_k(const QPartialArgs& a, bool div_exact, hipStream_t s) {
+    const unsigned g = grid_for(a.n, true);
+    if (a.K == 8 && !div_exact) delta_partial_q_kernel<GDT, WDT, 8, 0, FMT, EF><<<g, kBlock, 0, s>>>(a);
+    else if (div_exact) delta_partial_q_kernel<GDT, WDT, 0, 1, FMT, EF><<<g, kBlock, 0, s>>>(a);
+    else delta_partial_q_kernel<GDT, WDT, 0, 0, FMT, EF><<<g, kBlock, 0, s>>>(a);
+    return check_launch("delta_partial_q_kernel");
+}
+
+template <int GDT, int WDT>
+int launch_partial_q(const QPartialArgs& a, int fmt, bool div_exact, hipStream_t s) {
+    if (fmt == EDT_MXFP8)
+        return a.residual ? launch_partial_q_k<GDT, WDT, EDT_MXFP8, true>(a, div_exact, s)
+                          : launch_partial_q_k<GDT, WDT, EDT_MXFP8, false>(a, div_exact, s);
+    return a.residual ? launch_partial_q_k<GDT, WDT, EDT_MXFP4, true>(a, div_exact, s)
+                      : launch_partial_q_k<GDT, WDT, EDT_MXFP4, false>(a, div_exact, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t edt_q_region_bytes(uint64_t region_elems, int fmt) {
+    const int bits = fmt_bits(fmt);
+    if (!bits || region_elems % 512) return 0;
+    return region_elems / 8 * bits + region_elems / 32;
+}
+
+int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                        int K_total, uint64_t n, uint64_t region_elems, int fmt, float* residual, void* packed,
+                        void* stream) {
+    g_err[0] = 0;
+    if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
+    if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
+    if (K_local < 1 || K_local > EDT_MAX_WORKERS)
+        return fail(EDT_ERR_ARG, "worker count %d out of range [1, %d]", K_local, EDT_MAX_WORKERS);
+    if (K_total < 1) return fail(EDT_ERR_ARG, "total worker count %d < 1", K_total);
+    if (region_elems == 0 || region_elems % 512)
+        return fail(EDT_ERR_ARG, "region_elems %llu is not a positive multiple of 512", (unsigned long long)region_elems);
+    if (n % region_elems)
+        return fail(EDT_ERR_ARG, "n = %llu is not a whole number of regions of %llu elements", (unsigned long long)n,
+                    (unsigned long long)region_elems);
+    if (!theta_k) return fail(EDT_ERR_ARG, "theta_k is null");
+    if (n == 0) return EDT_OK;
+    if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
+    if (!packed) return fail(EDT_ERR_ARG, "packed is null");
+    QPartialArgs a;
+    memset(&a, 0, sizeof(a));
+    bool al = aligned16(theta_g) && aligned16(packed) && aligned16(residual);
+    for (int k = 0; k < K_local; ++k) {
+        if (!theta_k[k]) return fail(EDT_ERR_ARG, "theta_k[%d] is null", k);
+        a.w.p[k] = theta_k[k];
+        al = al && aligned16(theta_k[k]);
+    }
+    if (!al) return fail(EDT_ERR_ARG, "the quantized partial needs 16-byte aligned operands");
+    a.theta = theta_g;
+    a.residual = residual;
+    a.packed = static_cast<uint8_t*>(packed);
+    a.n = n;
+    a.tiles_per_region = region_elems / 512;
+    a.region_bytes = edt_q_region_bytes(region_elems, fmt);
+    a.payload_bytes = region_elems / 8 * fmt_bits(fmt);
+    a.K = K_local;
+    a.kdiv = (float)K_total;
+    a.kinv = 1.0f / (float)K_total;
+    const bool div_exact = !is_pow2(K_total);
+    hipStream_t s = (hipStream_t)stream;
+    if (gdt == EDT_F32 && wdt == EDT_F32) return launch_partial_q<EDT_F32, EDT_F32>(a, fmt, div_exact, s);
+    if (gdt == EDT_F32) return launch_partial_q<EDT_F32, EDT_BF16>(a, fmt, div_exact, s);
+    return launch_partial_q<EDT_BF16, EDT_BF16>(a, fmt, div_exact, s);
+}
+
+int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
+                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
+    g_err[0] = 0;
+    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
+    if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
+    if (nacc < 1 || nacc > EDT_MAX_WORKERS)
+        return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc, EDT_MAX_WORKERS);
+    if (n % 512) return fail(EDT_ERR_ARG, "n = %llu is not a multiple of 512 (one region)", (unsigned long long)n);
+    if (n == 0) return EDT_OK;
+    if (!theta_g || !regions) return fail(EDT_ERR_ARG, "null buffer");
+    SgdScalars s = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
+    if (s.use_momentum && !momentum) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    QRegions P;
+    memset(&P, 0, sizeof(P));
+    bool al = aligned16(theta_g) && (!s.use_momentum || aligned16(momentum));
+    for (int r = 0; r < nacc; ++r) {
+        if (!regions[r]) return fail(EDT_ERR_ARG, "regions[%d] is null", r);
+        P.p[r] = static_cast<const uint8_t*>(regions[r]);
+        al = al && aligned16(regions[r]);
+    }
+    if (!al) return fail(EDT_ERR_ARG, "the quantized sum needs 16-byte aligned operands");
+    const unsigned g = grid_for(n, true);
+    hipStream_t st = (hipStream_t)stream;
+    if (gdt == EDT_F32) {
+        if (fmt == EDT_MXFP8) sgd_apply_sum_q_kernel<EDT_F32, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+        else sgd_apply_sum_q_kernel<EDT_F32, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+    } else {
+        if (fmt == EDT_MXFP8) sgd_apply_sum_q_kernel<EDT_BF16, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+        else sgd_apply_sum_q_kernel<EDT_BF16, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+    }
+    return check_launch("sgd_apply_sum_q_kernel");
+}
+
+}  // extern "C"

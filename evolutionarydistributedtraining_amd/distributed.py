@@ -3,8 +3,8 @@
 The reference has no collectives: its "gather" is K x `from_pretrained` of the workers'
 checkpoints on a shared disk and its "broadcast" is K x `save_pretrained` (EDT_LM/diloco.py:
 231-235, 302-308). Here the population is resident in HBM across the node and the cross-replica
-mean is a real exchange step. Three schedules, all bucketed so RCCL traffic on the comm stream
-overlaps the HBM-bound kernels on the compute stream:
+mean is a real exchange step. Three schedules and one opt-in fourth, all bucketed so RCCL traffic
+on the comm stream overlaps the HBM-bound kernels on the compute stream:
 
   mode="reduce"          each rank fuses its local workers into an fp32 partial sum
                          (edt_delta_partial), reduce-scatter(sum, fp32) -> SGD on the owned shard
@@ -16,6 +16,16 @@ overlaps the HBM-bound kernels on the compute stream:
                          then edt_sgd_apply_sum: the owned shard's N partials summed in rank order
                          + SGD. Same wire bytes as reduce; one fixed summation order whatever RCCL
                          does (reproducible run to run, bit-exact with the oracle's split).
+  mode="reduce_q"        opt-in, never chosen by "auto": reduce_ordered with the partials block-quantized
+                         on the wire (wire_format="mxfp8" | "mxfp4": OCP MX blocks of 32 elements with
+                         one E8M0 scale byte). edt_delta_partial_q forms the fp32 partial
+                         in registers and writes only the packed regions [dest rank][payload | scales];
+                         the all-to-all moves uint8; edt_sgd_apply_sum_q dequantizes the owned shard's
+                         N regions, sums them in rank order and steps. Wire bytes: (N-1)/N * P *
+                         (q + b_g), q = 1 + 1/32 (mxfp8) or 1/2 + 1/32 (mxfp4) — computed from the
+                         byte counts, not measured on a multi-GPU node. error_feedback=True carries
+                         each rank's quantization error into its next step (`residual`, fp32, per
+                         rank: r = p' - D(Q(p')), p' = p + r_prev). Only with broadcast="theta".
   mode="exact"           all-to-all of the raw worker shards to their owners, then the single-GPU
                          fused kernel on each shard (the reference's worker order, bit-exact),
                          all-gather of theta. Wire bytes: (N-1)/N * P * (K_local * b_w + b_g).
@@ -51,16 +61,28 @@ def _timing_event():
     return torch.cuda.Event(enable_timing=True)
 
 
+_Q_BITS = {"mxfp8": 8, "mxfp4": 4}       # element bits of the reduce_q wire formats
+
+
 class ShardedOuterSync:
     def __init__(self, layout: ParamLayout, theta_dtype: torch.dtype, worker_dtype: torch.dtype,
                  k_local: int, device, lr: float = 0.7, momentum: float = 0.9, nesterov: bool = True,
                  mode: str = "auto", bucket_elems: int = 1 << 26, group=None, kernels=None,
                  broadcast: str = "auto", comm: Collectives | None = None,
-                 cpu_tails: tuple[int, int] | None = None):
-        if mode not in ("reduce", "reduce_ordered", "exact", "auto") or broadcast not in ("theta", "workers", "auto"):
+                 cpu_tails: tuple[int, int] | None = None, wire_format: str = "mxfp8",
+                 error_feedback: bool = True):
+        """mode="reduce_q": `wire_format` picks the element format of the quantized partials and
+        `error_feedback` keeps `self.residual` — this rank's fp32 quantization error (n_pad
+        elements), added to the next step's partial before it is quantized. The residual is per
+        rank (each rank quantizes its own partial) and is not part of theta or the momentum: a
+        restart without it loses at most one step's quantization error."""
+        if (mode not in ("reduce", "reduce_ordered", "reduce_q", "exact", "auto")
+                or broadcast not in ("theta", "workers", "auto")):
             raise ValueError((mode, broadcast))
         if mode.startswith("reduce") and broadcast == "workers":
             raise ValueError("the reduce schedules need the full theta replica (broadcast='theta')")
+        if mode == "reduce_q" and wire_format not in _Q_BITS:
+            raise ValueError(f"wire_format {wire_format!r}: 'mxfp8' or 'mxfp4'")
         check_sgd_hparams(lr, momentum, nesterov)
         # the communicator seam: torch.distributed (RCCL / gloo) by default, or N virtual ranks
         # on one device (collectives.VirtualWorld)
@@ -73,9 +95,11 @@ class ShardedOuterSync:
                  ("exact", "theta"): k_local * wb + gb, ("exact", "workers"): (k_local + 1) * wb}
         cands = {key: v for key, v in cands.items()
                  if mode in ("auto", key[0]) and broadcast in ("auto", key[1])}
+        if mode == "reduce_q":                         # opt-in only: never a candidate of "auto"
+            cands = {("reduce_q", "theta"): _Q_BITS[wire_format] / 8 + 1 / 32 + gb}
         # fewest wire bytes per element; ties go to the bit-exact schedule, then to the one whose
         # cross-rank sum has a fixed order (reduce_ordered) over RCCL's own (reduce)
-        pref = {"exact": 0, "reduce_ordered": 1, "reduce": 2}
+        pref = {"exact": 0, "reduce_ordered": 1, "reduce": 2, "reduce_q": 3}
         mode, broadcast = min(cands, key=lambda key: (cands[key], pref[key[0]], key[1] != "workers"))
         self.kernels = kernels or _ops
         self.mode = mode
@@ -85,8 +109,9 @@ class ShardedOuterSync:
         self.k_local = k_local
         self.k_total = k_local * self.world
         n = layout.total
-        # buckets: multiples of world * 64 elements so every shard is 16-byte aligned
-        unit = self.world * 64
+        # buckets: multiples of world * 64 elements so every shard is 16-byte aligned (reduce_q:
+        # world * 512, so every shard is a whole region of the wire format)
+        unit = self.world * (512 if mode == "reduce_q" else 64)
         bucket = max(unit, bucket_elems // unit * unit)
         self.n = n
         self.n_pad = math.ceil(n / unit) * unit
@@ -117,6 +142,13 @@ class ShardedOuterSync:
             # partials laid out [dest rank][shard] per bucket, received as [src rank][shard]
             self.acc = torch.zeros(self.n_pad, dtype=torch.float32, device=device)
             self.acc_recv = torch.zeros(self.n_pad, dtype=torch.float32, device=device)
+        elif mode == "reduce_q":
+            # per bucket `world` regions of one shard each, [dest rank][payload | scales], received
+            # as [src rank][payload | scales]; a bucket starts at byte _q_bytes(b) of both buffers
+            self.wire_format = wire_format
+            self.q_send = torch.zeros(self._q_bytes(self.n_pad), dtype=torch.uint8, device=device)
+            self.q_recv = torch.zeros(self._q_bytes(self.n_pad), dtype=torch.uint8, device=device)
+            self.residual = torch.zeros(self.n_pad, dtype=torch.float32, device=device) if error_feedback else None
         else:
             # recv[j][b:e] viewed [src rank][per]: local worker j of every rank, this rank's shard
             self.recv = [torch.empty(self.n_pad, dtype=worker_dtype, device=device) for _ in range(k_local)]
@@ -125,6 +157,12 @@ class ShardedOuterSync:
     def _shard(self, b, e):
         per = (e - b) // self.world
         return b + self.rank * per, b + (self.rank + 1) * per
+
+    def _q_bytes(self, elems: int) -> int:
+        """Packed bytes of `elems` elements (a multiple of 512) in this sync's wire format: the
+        payload and one scale byte per 32 elements. Linear in elems, so it is also the byte offset
+        of element offset `elems` in the send / receive buffers."""
+        return elems * _Q_BITS[self.wire_format] // 8 + elems // 32
 
     def _launch(self, fn, *args):
         """A local kernel, bracketed by timing events on its launch stream when
@@ -149,6 +187,12 @@ class ShardedOuterSync:
             return shard * (self.k_total * wb + 2 * gb + mom)
         if self.mode == "reduce_ordered":
             return self.n_pad * (self.k_local * wb + gb + 4) + shard * (4 * self.world + 2 * gb + mom)
+        if self.mode == "reduce_q":
+            # phase 1 writes q instead of 4 B per element (+ the residual read and written with
+            # error feedback); phase 2 reads N x q instead of N x 4 B per owned element
+            ef = 8 if self.residual is not None else 0
+            return (self.n_pad * (self.k_local * wb + gb + ef) + self._q_bytes(self.n_pad)
+                    + shard * (2 * gb + mom) + self.world * self._q_bytes(shard))
         return self.n_pad * (self.k_local * wb + gb + 4) + shard * (4 + 2 * gb + mom)
 
     @traced("edt/ShardedOuterSync.step")
@@ -194,6 +238,29 @@ class ShardedOuterSync:
                 parts = list(self.acc_recv[b:e].view(self.world, per))
                 mom = None if self.mom_shard is None else self.mom_shard[mom_off:mom_off + per]
                 self._launch(self._sgd_sum, self.theta_buf[s0:s1], parts, mom)
+                mom_off += per
+                gathers.append(self._gather(b, e, s0, s1))
+        elif self.mode == "reduce_q":
+            # reduce_ordered with quantized partials: phase 1 writes bucket [b, e) as `world` packed
+            # regions [dest rank][payload | scales] (the fp32 partial stays in registers), the
+            # all-to-all moves the bytes
+            works = []
+            for b, e in self.buckets:
+                per = (e - b) // self.world
+                qb, qe = self._q_bytes(b), self._q_bytes(e)
+                self._launch(k.delta_partial_q, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
+                             self.k_total, self.q_send[qb:qe], per, self.wire_format,
+                             None if self.residual is None else self.residual[b:e])
+                works.append(self.comm.all_to_all(self.q_recv[qb:qe], self.q_send[qb:qe], async_op=True))
+            # phase 2: the owned shard's N regions dequantized, summed in rank order + SGD
+            for (b, e), w in zip(self.buckets, works):
+                w.wait()
+                s0, s1 = self._shard(b, e)
+                per = s1 - s0
+                regions = list(self.q_recv[self._q_bytes(b):self._q_bytes(e)].view(self.world, self._q_bytes(per)))
+                mom = None if self.mom_shard is None else self.mom_shard[mom_off:mom_off + per]
+                self._launch(k.sgd_apply_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
+                             self.has_momentum, self.lr, self.momentum, self.nesterov)
                 mom_off += per
                 gathers.append(self._gather(b, e, s0, s1))
         else:
@@ -292,6 +359,8 @@ class ShardedOuterSync:
         f = (self.world - 1) / self.world
         bg = self.theta_buf.element_size()
         wb = self.worker_bufs[0].element_size()
+        if self.mode == "reduce_q":        # the packed partials + theta: (N-1)/N * P * (q + b_g)
+            return int(f * (self._q_bytes(self.n_pad) + self.n_pad * bg))
         if self.mode.startswith("reduce"):
             return int(f * self.n_pad * (4 + bg))
         return int(f * self.n_pad * (self.k_local * wb + (wb if self.broadcast == "workers" else bg)))

@@ -190,6 +190,71 @@ def sgd_apply_sum(theta: torch.Tensor, accs: list[torch.Tensor], momentum: torch
                                   L.stream_ptr(theta.device)), "edt_sgd_apply_sum")
 
 
+QFMT = {"mxfp8": L.EDT_MXFP8, "mxfp4": L.EDT_MXFP4}
+
+
+def _qfmt(fmt) -> int:
+    if fmt not in QFMT:
+        raise L.EdtError(f"unknown wire format {fmt!r}: 'mxfp8' or 'mxfp4'")
+    return QFMT[fmt]
+
+
+def q_region_bytes(region_elems: int, fmt) -> int:
+    """Bytes of one packed region of region_elems elements (a multiple of 512): the payload
+    (1 or 1/2 byte per element), then one E8M0 scale byte per 32 elements. Host only."""
+    if region_elems < 0 or region_elems % 512:
+        raise L.EdtError(f"region_elems {region_elems} is not a multiple of 512")
+    return int(L.load_library().edt_q_region_bytes(int(region_elems), _qfmt(fmt)))
+
+
+def delta_partial_q(theta: torch.Tensor, workers: list[torch.Tensor], k_total: int, packed: torch.Tensor,
+                    region_elems: int, fmt, residual: torch.Tensor | None = None) -> None:
+    """delta_partial's fp32 partial, block-quantized (fmt: 'mxfp8' | 'mxfp4', include/edt_sync.h)
+    into `packed` (uint8) as theta.numel() / region_elems regions back to back; the fp32 partial
+    never reaches HBM. residual (fp32, theta's size): error feedback, added before and rewritten
+    after the quantization (edt_delta_partial_q)."""
+    lib = L.lib()
+    if not workers:
+        raise L.EdtError("no workers")
+    L.require_device(theta, packed, residual, *workers)
+    n = theta.numel()
+    for w in workers:
+        if w.numel() != n or w.dtype != workers[0].dtype:
+            raise L.EdtError("every worker buffer must match theta's size and share one dtype")
+    code = _qfmt(fmt)
+    if region_elems <= 0 or region_elems % 512 or n % region_elems:
+        raise L.EdtError(f"region_elems {region_elems}: a multiple of 512 that divides theta's size {n}")
+    if packed.dtype != torch.uint8 or packed.numel() != n // region_elems * q_region_bytes(region_elems, fmt):
+        raise L.EdtError("packed: a uint8 buffer of theta.numel() / region_elems regions of q_region_bytes each")
+    if residual is not None and (residual.dtype != torch.float32 or residual.numel() != n):
+        raise L.EdtError("residual must be a float32 buffer of theta's size")
+    L.check(lib.edt_delta_partial_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
+                                    L.dtype_code(workers[0]), len(workers), int(k_total), n, int(region_elems), code,
+                                    L.ptr(residual), L.ptr(packed), L.stream_ptr(theta.device)),
+            "edt_delta_partial_q")
+
+
+def sgd_apply_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt, momentum: torch.Tensor | None,
+                    has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool) -> None:
+    """sgd_apply_sum on quantized partials: each of `regions` (uint8, q_region_bytes(theta.numel()))
+    is dequantized, they are summed in list order in fp32, then the SGD step on theta
+    (edt_sgd_apply_sum_q: the reduce_q schedule's per-shard step)."""
+    lib = L.lib()
+    L.require_device(theta, momentum, *regions)
+    n = theta.numel()
+    code = _qfmt(fmt)
+    if n % 512:
+        raise L.EdtError(f"theta's size {n} is not a multiple of 512 (one region)")
+    rb = q_region_bytes(n, fmt)
+    if not regions or any(r.dtype != torch.uint8 or r.numel() != rb for r in regions):
+        raise L.EdtError(f"regions: uint8 buffers of {rb} bytes (q_region_bytes of theta's size)")
+    if momentum is not None and (momentum.numel() != n or momentum.dtype != theta.dtype):
+        raise L.EdtError("momentum must have theta's size and dtype")
+    L.check(lib.edt_sgd_apply_sum_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code,
+                                    L.ptr(momentum), int(has_momentum), n, float(lr), float(momentum_coef),
+                                    int(nesterov), L.stream_ptr(theta.device)), "edt_sgd_apply_sum_q")
+
+
 def pair_merge(b1: torch.Tensor, b2: torch.Tensor | None, m1: torch.Tensor, m2: torch.Tensor,
                out: torch.Tensor, momentum: torch.Tensor | None, has_momentum: bool, lr: float,
                momentum_coef: float, nesterov: bool, momentum_in: torch.Tensor | None = None,

@@ -154,6 +154,44 @@ int edt_sgd_apply(void* theta_g, int gdt, const float* acc_f32, void* momentum, 
 int edt_sgd_apply_sum(void* theta_g, int gdt, const float* const* acc_f32, int nacc, void* momentum,
                       int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream);
 
+/* ---- block-quantized partial exchange (the sharded step's opt-in "reduce_q" schedule) --------
+ * The reference moves checkpoints over a shared disk (EDT_LM/diloco.py:231-235, 302-308) and has
+ * no wire format; reduce_ordered ships each rank's pseudo-gradient partial as fp32. These entries
+ * ship it as OCP MX blocks instead. Wire format:
+ *   block      32 consecutive elements of the fp32 partial share one E8M0 scale byte (bias 127)
+ *   scale      e = floor(log2(amax)) - emax, emax = 8 (E4M3) / 2 (E2M1); byte = clamp(e + 127, 0, 254);
+ *              an all-zero block (+-0) stores byte 0
+ *   elements   v * 2^-e rounded to nearest-even onto the element grid, saturating at +-448 (E4M3,
+ *              OCP encoding, never NaN) / +-6 (E2M1); the sign is kept, -0 included
+ *   non-finite a block holding any NaN or +-Inf stores scale byte 255 (elements: code 0); every
+ *              element of it dequantizes to NaN, so a diverged worker is never hidden
+ *   packing    MXFP8 one byte per element; MXFP4 element 2i in the low nibble, 2i+1 in the high
+ *              one. A region of R elements is R*bits/8 payload bytes followed by R/32 scale bytes;
+ *              R % 512 == 0, so payload and scales both start 16-byte aligned
+ *   D(q)       elem * 2^e, exact in fp32
+ * fp32 subnormal inputs are outside the bit-exact contract (finite output within one grid step). */
+typedef enum { EDT_MXFP8 = 0, EDT_MXFP4 = 1 } edt_qfmt_t;
+
+/* Bytes of one region of region_elems elements (HOST function; 0 for an unknown fmt or a
+ * region_elems that is not a multiple of 512). */
+uint64_t edt_q_region_bytes(uint64_t region_elems, int fmt);
+
+/* Phase 1: p = edt_delta_partial's fp32 partial (bit-identical, never written to HBM), quantized
+ * into `packed` as n / region_elems regions back to back ([dest rank][payload | scales] for one
+ * bucket of the schedule). residual (nullable, n floats): error feedback — p' = p + residual is
+ * what is quantized (one fp32 add) and residual = p' - D(q) is stored (one fp32 subtract).
+ * EDT_ERR_ARG when n % region_elems != 0, region_elems % 512 != 0, fmt is unknown, K is out of
+ * range or an operand is not 16-byte aligned. */
+int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                        int K_total, uint64_t n, uint64_t region_elems, int fmt, float* residual, void* packed,
+                        void* stream);
+
+/* Phase 2: edt_sgd_apply_sum on nacc quantized regions of n elements each (regions[0..nacc),
+ * device pointers): grad = -round_g(((D(q_0) + D(q_1)) + ...) + D(q_{nacc-1})) in fp32, that
+ * order, then the same SGD update. n % 512 == 0; operands 16-byte aligned. */
+int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
+                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream);
+
 /* ---- EDT pairwise merge -------------------------------------------------------------------
  * Replaces EDT_LM/train/crossover.py:150-163 + 166-230 for one child:
  *   B = lerp(0.5, b1, b2)                         (run_linear_merge_5050, in the model dtype wdt)

@@ -1,0 +1,132 @@
+"""Probe: the local kernels of one sharded outer step with fp32 partials (reduce_ordered, the
+baseline) against block-quantized partials (reduce_q: mxfp8 / mxfp4, error feedback on / off), on
+one GPU, 1.3B layout, K = 8, fp32 theta, bf16 and fp32 workers, at world 1 and as rank 0 of 8.
+
+One process, one rank: the communicator is a loopback (every peer's partial of the owned shard is
+a copy of this rank's own), so the kernels see the shapes, buffers and bytes of the N-rank step
+and nothing is measured of the links — the wire bytes of reduce_q are computed, not measured.
+Every kernel is bracketed by HIP events through ShardedOuterSync's kernel_events seam; a step's
+phase 1 is the sum of its edt_delta_partial(_q) launches, phase 2 of its edt_sgd_apply_sum(_q)
+launches; medians over --steps steps after --warmup. The baseline runs three times per group
+(first, middle, last), and its spread is recorded beside the numbers it judges.
+
+    python scripts/reduce_q_probe.py --out profiles/reduce_q_probe.json
+"""
+from __future__ import annotations
+
+import argparse
+import gc
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_BYTES_PER_MS = 8e9         # 8 TB/s
+
+
+def loopback(world: int):
+    from evolutionarydistributedtraining_amd.collectives import Collectives, _Done
+
+    class Loopback(Collectives):
+        """Rank 0 of `world` with no peers: an all-to-all delivers this rank's own region for its
+        shard from every source, an all-gather leaves the owned shard in place."""
+        inplace = True
+
+        def __init__(self):
+            self.world, self.rank = world, 0
+
+        def all_to_all(self, out, inp, async_op=False):
+            out.view(world, -1).copy_(inp.view(world, -1)[0].expand(world, -1))
+            return _Done()
+
+        def all_gather(self, out, inp, async_op=False):
+            return _Done()
+
+    return Loopback()
+
+
+def measure(layout, wdt, world, mode, fmt, ef, steps, warmup, dev, seed=0):
+    from evolutionarydistributedtraining_amd.distributed import ShardedOuterSync
+    k_local = 8 // world
+    s = ShardedOuterSync(layout, torch.float32, wdt, k_local, dev, mode=mode, broadcast="theta", comm=loopback(world),
+                         **({"wire_format": fmt, "error_feedback": ef} if mode == "reduce_q" else {}))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    s.theta_buf.normal_(0, 0.02, generator=g)
+    for w in s.worker_bufs:
+        w.copy_(s.theta_buf)
+        w.add_(torch.randn(s.n_pad, device=dev, generator=g).mul_(1e-3))
+    nb = len(s.buckets)
+    p1, p2 = [], []
+    for i in range(warmup + steps):
+        s.kernel_events = []
+        s.step()
+        torch.cuda.synchronize()
+        ms = [a.elapsed_time(b) for a, b in s.kernel_events]
+        assert len(ms) == 2 * nb
+        if i >= warmup:
+            p1.append(sum(ms[:nb]))
+            p2.append(sum(ms[nb:]))
+    tot = [a + b for a, b in zip(p1, p2)]
+    kb = s.kernel_bytes()
+    out = {"mode": mode, "wire_format": fmt, "error_feedback": ef, "buckets": nb, "n_pad": s.n_pad,
+           "phase1_ms": round(statistics.median(p1), 4), "phase2_ms": round(statistics.median(p2), 4),
+           "ms": round(statistics.median(tot), 4), "kernel_bytes": kb,
+           "fraction_of_8TBps": round(kb / statistics.median(tot) / PEAK_BYTES_PER_MS, 4),
+           "wire_bytes_computed": s.wire_bytes()}
+    del s
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--layout", default="gpt_1p3b")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reduce_q_probe.json"))
+    a = ap.parse_args()
+    from evolutionarydistributedtraining_amd import _lib as L
+    from evolutionarydistributedtraining_amd.layouts import LAYOUTS
+    dev = torch.device("cuda:0")
+    layout = LAYOUTS[a.layout]()
+    groups = []
+    for world in (1, 8):
+        for name, wdt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+            run = lambda mode, fmt=None, ef=None: measure(layout, wdt, world, mode, fmt, ef, a.steps, a.warmup, dev)
+            base = [run("reduce_ordered")]
+            rows = [run("reduce_q", "mxfp8", False), run("reduce_q", "mxfp8", True)]
+            base.append(run("reduce_ordered"))
+            rows += [run("reduce_q", "mxfp4", False), run("reduce_q", "mxfp4", True)]
+            base.append(run("reduce_ordered"))
+            b1 = [b["phase1_ms"] for b in base]
+            bt = [b["ms"] for b in base]
+            grp = {"world": world, "workers": name, "theta": "f32", "k_local": 8 // world,
+                   "baseline": dict(base[1], repeats_phase1_ms=b1, repeats_ms=bt,
+                                    phase1_ms=round(statistics.median(b1), 4), ms=round(statistics.median(bt), 4),
+                                    spread_phase1_ms=round(max(b1) - min(b1), 4), spread_ms=round(max(bt) - min(bt), 4)),
+                   "reduce_q": rows}
+            # the merge condition: phase 1 without error feedback is not slower than edt_delta_partial
+            # on the same operands by more than the baseline's own spread
+            grp["phase1_not_slower"] = {r["wire_format"]: r["phase1_ms"] <= grp["baseline"]["phase1_ms"]
+                                        + grp["baseline"]["spread_phase1_ms"]
+                                        for r in rows if not r["error_feedback"]}
+            groups.append(grp)
+            print(json.dumps(grp), flush=True)
+    res = {"probe": "reduce_q_probe", "layout": a.layout, "elements": layout.total, "K": 8, "steps": a.steps,
+           "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "library_sha256": L.library_sha256(),
+           "note": "local kernels only, one GPU, loopback communicator; wire_bytes_computed follow from the byte "
+                   "counts and were not measured on a multi-GPU node", "groups": groups}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
