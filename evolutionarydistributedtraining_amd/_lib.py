@@ -47,6 +47,8 @@ SIGNATURES = [
     ("edt_q_region_bytes", _U64, [_U64, _I]),
     ("edt_delta_partial_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _U64, _I, _P, _P, _P]),
     ("edt_sgd_apply_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P]),
+    ("edt_sgd_delta_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _P, _I, _P]),
+    ("edt_apply_delta_q", _I, [_P, _I, _P, _U64, _U64, _I, _P]),
     ("edt_pair_merge", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_to", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_population", _I, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),

@@ -3,9 +3,11 @@
 // (edt_delta_partial's math, bit for bit) and writes it as OCP MX blocks — MXFP8 (E4M3 elements)
 // or MXFP4 (E2M1 elements), 32 elements per E8M0 scale byte — without the fp32 partial ever
 // reaching HBM; phase 2 dequantizes the owned shard's N regions, sums them in rank order
-// (edt_sgd_apply_sum's order) and runs the SGD step. The reference ships checkpoints over a shared
-// disk (EDT_LM/diloco.py:231-235) and has no wire format; this one is defined here and in
-// DESIGN.md §3.
+// (edt_sgd_apply_sum's order) and runs the SGD step. With the quantized gather (gather_format) the
+// owner runs phase 2' instead: the same step, but theta is left alone and the update theta' - theta
+// is written as one more region (sharded error feedback); phase 3 then adds the dequantized updates
+// of a whole bucket to theta on every rank. The reference ships checkpoints over a shared disk
+// (EDT_LM/diloco.py:231-235) and has no wire format; this one is defined here and in DESIGN.md §3.
 //
 // Wire format (the definition; tests/quant_reference.py restates it in numpy)
 //   block     32 consecutive elements of a rank's fp32 partial share one E8M0 scale byte (bias 127)
@@ -90,10 +92,73 @@ __device__ __forceinline__ float q_decode(uint32_t c) {
     return __uint_as_float((c + ((uint32_t)(127 - F::BIAS) << F::MB)) << (23 - F::MB));
 }
 
+// The quantize-and-store tail shared by phase 1 and phase 2': the 8 values v at element `off` of the
+// region at `base` (off a multiple of 8; the wave's 64 lanes cover 512 consecutive elements of one
+// region) become codes under their block's scale; with EF the residual v - D(q) goes to res[i].
+template <int FMT, bool EF>
+__device__ __forceinline__ void quant_store(const float (&acc)[kVec], float* res, uint64_t i, uint8_t* base,
+                                            uint64_t off, uint64_t payload_bytes) {
+    using F = QFmt<FMT>;
+    constexpr int N = kVec;
+    // block amax over the bit patterns of |v| (monotone for finite values; NaN / Inf compare highest)
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint32_t u = __float_as_uint(acc[j]) & 0x7fffffffu;
+        m = u > m ? u : m;
+    }
+    uint32_t o = (uint32_t)__shfl_xor((int)m, 1);
+    m = o > m ? o : m;
+    o = (uint32_t)__shfl_xor((int)m, 2);
+    m = o > m ? o : m;
+    const bool bad = m >= 0x7f800000u;
+    int sb = (int)(m >> 23) - F::EMAX;                   // e + 127
+    sb = sb < 0 ? 0 : sb;
+    if (bad) sb = 255;
+    // v * 2^-e = v * 2^(127 - sb): one exact multiply; back by 2^e as two exact factors, since
+    // 2^-127 (scale byte 0) is no normal fp32
+    const int up = bad ? 0 : 127 - sb;                   // -125 .. 127
+    const float su = pow2f(up);
+    const float d0 = pow2f(up > 64 ? -64 : -up), d1 = pow2f(up > 64 ? 64 - up : 0);
+    uint32_t code[N];
+    float deq[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint32_t sign = __float_as_uint(acc[j]) & 0x80000000u;
+        const float ax = __uint_as_float(__float_as_uint(acc[j]) & 0x7fffffffu) * su;
+        const float r = q_round<FMT>(bad ? 0.f : ax);
+        code[j] = bad ? 0u : (q_code<FMT>(r) | (sign >> (32 - F::BITS)));
+        deq[j] = bad ? __builtin_nanf("") : __uint_as_float(__float_as_uint(r * d0 * d1) | sign);   // D(q)
+    }
+    if constexpr (EF) {
+        float r[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) r[j] = acc[j] - deq[j];          // r = p' - D(q)
+        st<EDT_F32, N, false>(res, i, r);
+    }
+    if constexpr (FMT == EDT_MXFP8) {
+        u32x2 v;
+        v.x = code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24);
+        v.y = code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24);
+        *reinterpret_cast<u32x2*>(base + off) = v;
+    } else {
+        uint32_t v = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) v |= code[j] << (4 * j);
+        *reinterpret_cast<uint32_t*>(base + (off >> 1)) = v;
+    }
+    // the wave's 16 scale bytes: lanes 4b .. 4b+3 hold block b's; each group of 16 lanes gathers
+    // its four into one dword by an or-butterfly, and its first lane stores it
+    const unsigned lane = threadIdx.x & 63u;
+    uint32_t sw = (uint32_t)sb << (8 * ((lane >> 2) & 3u));
+    sw |= (uint32_t)__shfl_xor((int)sw, 4);
+    sw |= (uint32_t)__shfl_xor((int)sw, 8);
+    if ((lane & 15u) == 0) *reinterpret_cast<uint32_t*>(base + payload_bytes + (off >> 5)) = sw;
+}
+
 // Phase 1 for the 8 elements at i (a multiple of 8; the wave's 64 lanes cover 512 consecutive ones).
 template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
 __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t i) {
-    using F = QFmt<FMT>;
     constexpr int N = kVec;
     float g[N], acc[N];
     ld<GDT, N, (EDT_NT_RMW != 0)>(a.theta, i, g);
@@ -131,42 +196,6 @@ __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t 
 #pragma unroll
         for (int j = 0; j < N; ++j) acc[j] = acc[j] + r[j];          // p' = p + r
     }
-    // block amax over the bit patterns of |v| (monotone for finite values; NaN / Inf compare highest)
-    uint32_t m = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const uint32_t u = __float_as_uint(acc[j]) & 0x7fffffffu;
-        m = u > m ? u : m;
-    }
-    uint32_t o = (uint32_t)__shfl_xor((int)m, 1);
-    m = o > m ? o : m;
-    o = (uint32_t)__shfl_xor((int)m, 2);
-    m = o > m ? o : m;
-    const bool bad = m >= 0x7f800000u;
-    int sb = (int)(m >> 23) - F::EMAX;                   // e + 127
-    sb = sb < 0 ? 0 : sb;
-    if (bad) sb = 255;
-    // v * 2^-e = v * 2^(127 - sb): one exact multiply; back by 2^e as two exact factors, since
-    // 2^-127 (scale byte 0) is no normal fp32
-    const int up = bad ? 0 : 127 - sb;                   // -125 .. 127
-    const float su = pow2f(up);
-    const float d0 = pow2f(up > 64 ? -64 : -up), d1 = pow2f(up > 64 ? 64 - up : 0);
-    uint32_t code[N];
-    float deq[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const uint32_t sign = __float_as_uint(acc[j]) & 0x80000000u;
-        const float ax = __uint_as_float(__float_as_uint(acc[j]) & 0x7fffffffu) * su;
-        const float r = q_round<FMT>(bad ? 0.f : ax);
-        code[j] = bad ? 0u : (q_code<FMT>(r) | (sign >> (32 - F::BITS)));
-        deq[j] = bad ? __builtin_nanf("") : __uint_as_float(__float_as_uint(r * d0 * d1) | sign);   // D(q)
-    }
-    if constexpr (EF) {
-        float r[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) r[j] = acc[j] - deq[j];          // r = p' - D(q)
-        st<EDT_F32, N, false>(a.residual, i, r);
-    }
     // addresses: tile = 512 elements = one wave; a region is a whole number of tiles
     const uint64_t tile = i >> 9;
     uint64_t reg;
@@ -174,24 +203,7 @@ __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t 
     else reg = (uint32_t)tile / (uint32_t)a.tiles_per_region;
     const uint64_t off = i - reg * (a.tiles_per_region << 9);        // element offset inside the region
     uint8_t* base = a.packed + reg * a.region_bytes;
-    if constexpr (FMT == EDT_MXFP8) {
-        u32x2 v;
-        v.x = code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24);
-        v.y = code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24);
-        *reinterpret_cast<u32x2*>(base + off) = v;
-    } else {
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < N; ++j) v |= code[j] << (4 * j);
-        *reinterpret_cast<uint32_t*>(base + (off >> 1)) = v;
-    }
-    // the wave's 16 scale bytes: lanes 4b .. 4b+3 hold block b's; each group of 16 lanes gathers
-    // its four into one dword by an or-butterfly, and its first lane stores it
-    const unsigned lane = threadIdx.x & 63u;
-    uint32_t sw = (uint32_t)sb << (8 * ((lane >> 2) & 3u));
-    sw |= (uint32_t)__shfl_xor((int)sw, 4);
-    sw |= (uint32_t)__shfl_xor((int)sw, 8);
-    if ((lane & 15u) == 0) *reinterpret_cast<uint32_t*>(base + a.payload_bytes + (off >> 5)) = sw;
+    quant_store<FMT, EF>(acc, a.residual, i, base, off, a.payload_bytes);
 }
 
 template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
@@ -258,6 +270,67 @@ __global__ __launch_bounds__(kBlock) void sgd_apply_sum_q_kernel(void* theta, QR
     }
 }
 
+// phase 2': sgd_apply_sum_q_kernel's step on the owned shard, but theta stays as it is: the update
+// u = theta' - theta (+ the owner's residual with EF) leaves as one region of FOUT blocks
+template <int GDT, int FIN, int FOUT, bool EF>
+__global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_kernel(const void* theta, QRegions P, int np, void* mom,
+                                                                 uint64_t n, SgdScalars s, float* residual,
+                                                                 uint8_t* packed_out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t nv = n / kVec;                        // n % 512 == 0: a wave is in or out as a whole
+    const uint64_t payload = n / 8 * QFmt<FOUT>::BITS;
+    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
+        const uint64_t i = v * kVec;
+        float g0[kVec], g[kVec], a[kVec], grad[kVec], b_in[kVec];
+        ld<GDT, kVec>(theta, i, g0);
+        ld_momentum<GDT, kVec>(mom, i, s, b_in);
+        ld_q<FIN>(P.p[0], n, i, a);
+        for (int r = 1; r < np; ++r) {                  // rank order, as sgd_apply_sum_q_kernel
+            float x[kVec];
+            ld_q<FIN>(P.p[r], n, i, x);
+#pragma unroll
+            for (int j = 0; j < kVec; ++j) a[j] = a[j] + x[j];
+        }
+        rnd<GDT>(a);
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) { grad[j] = -a[j]; g[j] = g0[j]; }
+        sgd_update<GDT, kVec>(g, grad, mom, i, s, b_in);
+        float u[kVec];
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) u[j] = g[j] - g0[j];               // u = theta' - theta
+        if constexpr (EF) {
+            float r[kVec];
+            ld<EDT_F32, kVec>(residual, i, r);
+#pragma unroll
+            for (int j = 0; j < kVec; ++j) u[j] = u[j] + r[j];            // u' = u + r_g
+        }
+        quant_store<FOUT, EF>(u, residual, i, packed_out, i, payload);
+    }
+}
+
+// phase 3: theta <- round_g(theta + D(q)) over a bucket of n / region_elems regions back to back
+template <int GDT, int FMT>
+__global__ __launch_bounds__(kBlock) void apply_delta_q_kernel(void* theta, const uint8_t* packed, uint64_t n,
+                                                               uint64_t tiles_per_region, uint64_t region_bytes) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t nv = n / kVec;
+    const uint64_t region_elems = tiles_per_region << 9;
+    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
+        const uint64_t i = v * kVec;
+        const uint64_t tile = i >> 9;
+        uint64_t reg;
+        if ((tile | tiles_per_region) >> 32) reg = tile / tiles_per_region;
+        else reg = (uint32_t)tile / (uint32_t)tiles_per_region;
+        float g[kVec], d[kVec];
+        ld<GDT, kVec>(theta, i, g);
+        ld_q<FMT>(packed + reg * region_bytes, region_elems, i - reg * region_elems, d);
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) g[j] = g[j] + d[j];
+        rnd<GDT>(g);
+        st<GDT, kVec>(theta, i, g);
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // launch helpers
 
@@ -279,6 +352,27 @@ int launch_partial_q(const QPartialArgs& a, int fmt, bool div_exact, hipStream_t
                           : launch_partial_q_k<GDT, WDT, EDT_MXFP8, false>(a, div_exact, s);
     return a.residual ? launch_partial_q_k<GDT, WDT, EDT_MXFP4, true>(a, div_exact, s)
                       : launch_partial_q_k<GDT, WDT, EDT_MXFP4, false>(a, div_exact, s);
+}
+
+template <int GDT, int FIN, int FOUT>
+void launch_delta_sum_q_e(const void* theta, const QRegions& P, int np, void* mom, uint64_t n, const SgdScalars& sc,
+                          float* residual, uint8_t* out, hipStream_t s) {
+    const unsigned g = grid_for(n, true);
+    if (residual) sgd_delta_sum_q_kernel<GDT, FIN, FOUT, true><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out);
+    else sgd_delta_sum_q_kernel<GDT, FIN, FOUT, false><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out);
+}
+
+template <int GDT>
+void launch_delta_sum_q(const void* theta, const QRegions& P, int np, int fmt_in, void* mom, uint64_t n,
+                        const SgdScalars& sc, float* residual, uint8_t* out, int fmt_out, hipStream_t s) {
+    if (fmt_in == EDT_MXFP8 && fmt_out == EDT_MXFP8)
+        launch_delta_sum_q_e<GDT, EDT_MXFP8, EDT_MXFP8>(theta, P, np, mom, n, sc, residual, out, s);
+    else if (fmt_in == EDT_MXFP8)
+        launch_delta_sum_q_e<GDT, EDT_MXFP8, EDT_MXFP4>(theta, P, np, mom, n, sc, residual, out, s);
+    else if (fmt_out == EDT_MXFP8)
+        launch_delta_sum_q_e<GDT, EDT_MXFP4, EDT_MXFP8>(theta, P, np, mom, n, sc, residual, out, s);
+    else
+        launch_delta_sum_q_e<GDT, EDT_MXFP4, EDT_MXFP4>(theta, P, np, mom, n, sc, residual, out, s);
 }
 
 }  // namespace
@@ -366,6 +460,66 @@ int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int 
         else sgd_apply_sum_q_kernel<EDT_BF16, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
     }
     return check_launch("sgd_apply_sum_q_kernel");
+}
+
+int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in, void* momentum,
+                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, float* residual,
+                        void* packed_out, int fmt_out, void* stream) {
+    g_err[0] = 0;
+    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
+    if (!fmt_bits(fmt_in)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt_in);
+    if (!fmt_bits(fmt_out)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt_out);
+    if (nacc < 1 || nacc > EDT_MAX_WORKERS)
+        return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc, EDT_MAX_WORKERS);
+    if (n % 512) return fail(EDT_ERR_ARG, "n = %llu is not a multiple of 512 (one region)", (unsigned long long)n);
+    if (n == 0) return EDT_OK;
+    if (!theta_g || !regions) return fail(EDT_ERR_ARG, "null buffer");
+    if (!packed_out) return fail(EDT_ERR_ARG, "packed_out is null");
+    SgdScalars s = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
+    if (s.use_momentum && !momentum) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    QRegions P;
+    memset(&P, 0, sizeof(P));
+    bool al = aligned16(theta_g) && (!s.use_momentum || aligned16(momentum)) && aligned16(residual) && aligned16(packed_out);
+    for (int r = 0; r < nacc; ++r) {
+        if (!regions[r]) return fail(EDT_ERR_ARG, "regions[%d] is null", r);
+        P.p[r] = static_cast<const uint8_t*>(regions[r]);
+        al = al && aligned16(regions[r]);
+    }
+    if (!al) return fail(EDT_ERR_ARG, "the quantized update needs 16-byte aligned operands");
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* out = static_cast<uint8_t*>(packed_out);
+    if (gdt == EDT_F32) launch_delta_sum_q<EDT_F32>(theta_g, P, nacc, fmt_in, momentum, n, s, residual, out, fmt_out, st);
+    else launch_delta_sum_q<EDT_BF16>(theta_g, P, nacc, fmt_in, momentum, n, s, residual, out, fmt_out, st);
+    return check_launch("sgd_delta_sum_q_kernel");
+}
+
+int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
+                      void* stream) {
+    g_err[0] = 0;
+    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
+    if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
+    if (region_elems == 0 || region_elems % 512)
+        return fail(EDT_ERR_ARG, "region_elems %llu is not a positive multiple of 512", (unsigned long long)region_elems);
+    if (n % region_elems)
+        return fail(EDT_ERR_ARG, "n = %llu is not a whole number of regions of %llu elements", (unsigned long long)n,
+                    (unsigned long long)region_elems);
+    if (n == 0) return EDT_OK;
+    if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
+    if (!packed) return fail(EDT_ERR_ARG, "packed is null");
+    if (!aligned16(theta_g) || !aligned16(packed))
+        return fail(EDT_ERR_ARG, "the quantized update needs 16-byte aligned operands");
+    const unsigned g = grid_for(n, true);
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* q = static_cast<const uint8_t*>(packed);
+    const uint64_t tpr = region_elems / 512, rb = edt_q_region_bytes(region_elems, fmt);
+    if (gdt == EDT_F32) {
+        if (fmt == EDT_MXFP8) apply_delta_q_kernel<EDT_F32, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
+        else apply_delta_q_kernel<EDT_F32, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
+    } else {
+        if (fmt == EDT_MXFP8) apply_delta_q_kernel<EDT_BF16, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
+        else apply_delta_q_kernel<EDT_BF16, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
+    }
+    return check_launch("apply_delta_q_kernel");
 }
 
 }  // extern "C"

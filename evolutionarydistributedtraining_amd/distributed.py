@@ -26,6 +26,18 @@ on the comm stream overlaps the HBM-bound kernels on the compute stream:
                          byte counts, not measured on a multi-GPU node. error_feedback=True carries
                          each rank's quantization error into its next step (`residual`, fp32, per
                          rank: r = p' - D(Q(p')), p' = p + r_prev). Only with broadcast="theta".
+    gather_format="mxfp8" | "mxfp4" (reduce_q only, opt-in) quantizes the other half of the
+                         exchange: the owner runs edt_sgd_delta_sum_q instead — the same sum and SGD
+                         update, the same momentum bits, but theta is left alone and the update
+                         u = theta' - theta is written as one more packed region, straight into this
+                         rank's slot of `u_recv` ([src rank][payload | scales]); a uint8 all-gather
+                         replaces the all-gather of theta, and as each bucket lands
+                         edt_apply_delta_q adds the dequantized updates to theta — the same kernel
+                         on the same bytes on every rank, so the replicas stay bit-identical.
+                         error_feedback also keeps `residual_g` (fp32, sharded like the momentum:
+                         u' = u + r_g, r_g = u' - D(Q(u'))). Wire bytes: (N-1)/N * P * (q_in + q_out)
+                         — 2.0625 B/elem with mxfp8 both ways whatever theta's dtype; computed from
+                         the byte counts, not measured on a multi-GPU node.
   mode="exact"           all-to-all of the raw worker shards to their owners, then the single-GPU
                          fused kernel on each shard (the reference's worker order, bit-exact),
                          all-gather of theta. Wire bytes: (N-1)/N * P * (K_local * b_w + b_g).
@@ -70,12 +82,15 @@ class ShardedOuterSync:
                  mode: str = "auto", bucket_elems: int = 1 << 26, group=None, kernels=None,
                  broadcast: str = "auto", comm: Collectives | None = None,
                  cpu_tails: tuple[int, int] | None = None, wire_format: str = "mxfp8",
-                 error_feedback: bool = True):
+                 error_feedback: bool = True, gather_format: str | None = None):
         """mode="reduce_q": `wire_format` picks the element format of the quantized partials and
         `error_feedback` keeps `self.residual` — this rank's fp32 quantization error (n_pad
         elements), added to the next step's partial before it is quantized. The residual is per
         rank (each rank quantizes its own partial) and is not part of theta or the momentum: a
-        restart without it loses at most one step's quantization error."""
+        restart without it loses at most one step's quantization error. `gather_format` (reduce_q
+        only) ships the owners' quantized updates instead of theta (module docstring); with
+        error_feedback it keeps `self.residual_g`, the owner's fp32 error of that quantization
+        (sharded like the momentum), under the same restart rule."""
         if (mode not in ("reduce", "reduce_ordered", "reduce_q", "exact", "auto")
                 or broadcast not in ("theta", "workers", "auto")):
             raise ValueError((mode, broadcast))
@@ -83,6 +98,11 @@ class ShardedOuterSync:
             raise ValueError("the reduce schedules need the full theta replica (broadcast='theta')")
         if mode == "reduce_q" and wire_format not in _Q_BITS:
             raise ValueError(f"wire_format {wire_format!r}: 'mxfp8' or 'mxfp4'")
+        if gather_format is not None:
+            if mode != "reduce_q":
+                raise ValueError("gather_format quantizes the gather of mode='reduce_q' only")
+            if gather_format not in _Q_BITS:
+                raise ValueError(f"gather_format {gather_format!r}: None, 'mxfp8' or 'mxfp4'")
         check_sgd_hparams(lr, momentum, nesterov)
         # the communicator seam: torch.distributed (RCCL / gloo) by default, or N virtual ranks
         # on one device (collectives.VirtualWorld)
@@ -149,6 +169,13 @@ class ShardedOuterSync:
             self.q_send = torch.zeros(self._q_bytes(self.n_pad), dtype=torch.uint8, device=device)
             self.q_recv = torch.zeros(self._q_bytes(self.n_pad), dtype=torch.uint8, device=device)
             self.residual = torch.zeros(self.n_pad, dtype=torch.float32, device=device) if error_feedback else None
+            self.gather_format = gather_format
+            if gather_format is not None:
+                # the owners' updates of a bucket, [src rank][payload | scales], from byte
+                # _q_bytes(b, gather_format); this rank writes its own slot, the all-gather the rest
+                self.u_recv = torch.zeros(self._q_bytes(self.n_pad, gather_format), dtype=torch.uint8, device=device)
+                self.residual_g = (torch.zeros(shard_total, dtype=torch.float32, device=device)
+                                   if error_feedback else None)
         else:
             # recv[j][b:e] viewed [src rank][per]: local worker j of every rank, this rank's shard
             self.recv = [torch.empty(self.n_pad, dtype=worker_dtype, device=device) for _ in range(k_local)]
@@ -158,11 +185,11 @@ class ShardedOuterSync:
         per = (e - b) // self.world
         return b + self.rank * per, b + (self.rank + 1) * per
 
-    def _q_bytes(self, elems: int) -> int:
-        """Packed bytes of `elems` elements (a multiple of 512) in this sync's wire format: the
-        payload and one scale byte per 32 elements. Linear in elems, so it is also the byte offset
-        of element offset `elems` in the send / receive buffers."""
-        return elems * _Q_BITS[self.wire_format] // 8 + elems // 32
+    def _q_bytes(self, elems: int, fmt: str | None = None) -> int:
+        """Packed bytes of `elems` elements (a multiple of 512) in this sync's wire format (or in
+        `fmt`): the payload and one scale byte per 32 elements. Linear in elems, so it is also the
+        byte offset of element offset `elems` in the send / receive buffers."""
+        return elems * _Q_BITS[fmt or self.wire_format] // 8 + elems // 32
 
     def _launch(self, fn, *args):
         """A local kernel, bracketed by timing events on its launch stream when
@@ -191,8 +218,15 @@ class ShardedOuterSync:
             # phase 1 writes q instead of 4 B per element (+ the residual read and written with
             # error feedback); phase 2 reads N x q instead of N x 4 B per owned element
             ef = 8 if self.residual is not None else 0
-            return (self.n_pad * (self.k_local * wb + gb + ef) + self._q_bytes(self.n_pad)
-                    + shard * (2 * gb + mom) + self.world * self._q_bytes(shard))
+            p1 = self.n_pad * (self.k_local * wb + gb + ef) + self._q_bytes(self.n_pad)
+            if self.gather_format is not None:
+                # phase 2' reads theta, the momentum and N regions, writes the momentum and one
+                # region (+ its residual read and written); phase 3 reads and writes theta over the
+                # whole arena and reads every owner's region
+                gf = self.gather_format
+                return (p1 + shard * (gb + mom + ef) + self.world * self._q_bytes(shard) + self._q_bytes(shard, gf)
+                        + self.n_pad * 2 * gb + self._q_bytes(self.n_pad, gf))
+            return p1 + shard * (2 * gb + mom) + self.world * self._q_bytes(shard)
         return self.n_pad * (self.k_local * wb + gb + 4) + shard * (4 + 2 * gb + mom)
 
     @traced("edt/ShardedOuterSync.step")
@@ -259,10 +293,29 @@ class ShardedOuterSync:
                 per = s1 - s0
                 regions = list(self.q_recv[self._q_bytes(b):self._q_bytes(e)].view(self.world, self._q_bytes(per)))
                 mom = None if self.mom_shard is None else self.mom_shard[mom_off:mom_off + per]
-                self._launch(k.sgd_apply_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
-                             self.has_momentum, self.lr, self.momentum, self.nesterov)
+                if self.gather_format is None:
+                    self._launch(k.sgd_apply_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
+                                 self.has_momentum, self.lr, self.momentum, self.nesterov)
+                    gathers.append(self._gather(b, e, s0, s1))
+                else:
+                    # phase 2': the quantized update of the owned shard into this rank's slot of
+                    # u_recv (theta untouched), then the all-gather of the packed bytes
+                    gf = self.gather_format
+                    ub, ur = self._q_bytes(b, gf), self._q_bytes(per, gf)
+                    slot = self.u_recv[ub + self.rank * ur:ub + (self.rank + 1) * ur]
+                    res_g = None if self.residual_g is None else self.residual_g[mom_off:mom_off + per]
+                    self._launch(k.sgd_delta_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
+                                 self.has_momentum, self.lr, self.momentum, self.nesterov, slot, gf, res_g)
+                    src = slot if self.inplace else slot.clone()
+                    gathers.append(self.comm.all_gather(self.u_recv[ub:self._q_bytes(e, gf)], src, async_op=True))
                 mom_off += per
-                gathers.append(self._gather(b, e, s0, s1))
+            if self.gather_format is not None:
+                # phase 3: as each bucket's updates land, every rank adds the same D(q) to its replica
+                for (b, e), g in zip(self.buckets, gathers):
+                    g.wait()
+                    gf = self.gather_format
+                    self._launch(k.apply_delta_q, self.theta_buf[b:e], self.u_recv[self._q_bytes(b, gf):self._q_bytes(e, gf)],
+                                 (e - b) // self.world, gf)
         else:
             # phase 1: every bucket's all-to-all, straight from the worker arenas (a worker's
             # bucket [b, e) is already laid out [dest rank][per]); one collective per local worker
@@ -359,6 +412,8 @@ class ShardedOuterSync:
         f = (self.world - 1) / self.world
         bg = self.theta_buf.element_size()
         wb = self.worker_bufs[0].element_size()
+        if self.mode == "reduce_q" and self.gather_format is not None:     # packed both ways
+            return int(f * (self._q_bytes(self.n_pad) + self._q_bytes(self.n_pad, self.gather_format)))
         if self.mode == "reduce_q":        # the packed partials + theta: (N-1)/N * P * (q + b_g)
             return int(f * (self._q_bytes(self.n_pad) + self.n_pad * bg))
         if self.mode.startswith("reduce"):

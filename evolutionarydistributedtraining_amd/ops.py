@@ -255,6 +255,51 @@ def sgd_apply_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt, momen
                                     int(nesterov), L.stream_ptr(theta.device)), "edt_sgd_apply_sum_q")
 
 
+def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, momentum: torch.Tensor | None,
+                    has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool, packed_out: torch.Tensor,
+                    fmt_out, residual: torch.Tensor | None = None) -> None:
+    """sgd_apply_sum_q's step on the owned shard with theta left as it is: the momentum is updated
+    (the same bits), and the update theta' - theta is block-quantized in fmt_out into `packed_out`
+    (uint8, q_region_bytes(theta.numel(), fmt_out): one region). residual (fp32, theta's size): the
+    owner's error feedback, added before and rewritten after the quantization
+    (edt_sgd_delta_sum_q: the quantized gather's phase 2')."""
+    lib = L.lib()
+    L.require_device(theta, momentum, packed_out, residual, *regions)
+    n = theta.numel()
+    code_in, code_out = _qfmt(fmt_in), _qfmt(fmt_out)
+    if n % 512:
+        raise L.EdtError(f"theta's size {n} is not a multiple of 512 (one region)")
+    rb = q_region_bytes(n, fmt_in)
+    if not regions or any(r.dtype != torch.uint8 or r.numel() != rb for r in regions):
+        raise L.EdtError(f"regions: uint8 buffers of {rb} bytes (q_region_bytes of theta's size)")
+    if momentum is not None and (momentum.numel() != n or momentum.dtype != theta.dtype):
+        raise L.EdtError("momentum must have theta's size and dtype")
+    if packed_out.dtype != torch.uint8 or packed_out.numel() != q_region_bytes(n, fmt_out):
+        raise L.EdtError("packed_out: a uint8 buffer of q_region_bytes(theta's size, fmt_out)")
+    if residual is not None and (residual.dtype != torch.float32 or residual.numel() != n):
+        raise L.EdtError("residual must be a float32 buffer of theta's size")
+    L.check(lib.edt_sgd_delta_sum_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code_in,
+                                    L.ptr(momentum), int(has_momentum), n, float(lr), float(momentum_coef),
+                                    int(nesterov), L.ptr(residual), L.ptr(packed_out), code_out,
+                                    L.stream_ptr(theta.device)), "edt_sgd_delta_sum_q")
+
+
+def apply_delta_q(theta: torch.Tensor, packed: torch.Tensor, region_elems: int, fmt) -> None:
+    """theta = round(theta + D(q)) in place: `packed` (uint8) holds theta.numel() / region_elems
+    regions back to back, delta_partial_q's layout (edt_apply_delta_q: the quantized gather's
+    phase 3, run with the same bytes on every rank)."""
+    lib = L.lib()
+    L.require_device(theta, packed)
+    n = theta.numel()
+    code = _qfmt(fmt)
+    if region_elems <= 0 or region_elems % 512 or n % region_elems:
+        raise L.EdtError(f"region_elems {region_elems}: a multiple of 512 that divides theta's size {n}")
+    if packed.dtype != torch.uint8 or packed.numel() != n // region_elems * q_region_bytes(region_elems, fmt):
+        raise L.EdtError("packed: a uint8 buffer of theta.numel() / region_elems regions of q_region_bytes each")
+    L.check(lib.edt_apply_delta_q(L.ptr(theta), L.dtype_code(theta), L.ptr(packed), n, int(region_elems), code,
+                                  L.stream_ptr(theta.device)), "edt_apply_delta_q")
+
+
 def pair_merge(b1: torch.Tensor, b2: torch.Tensor | None, m1: torch.Tensor, m2: torch.Tensor,
                out: torch.Tensor, momentum: torch.Tensor | None, has_momentum: bool, lr: float,
                momentum_coef: float, nesterov: bool, momentum_in: torch.Tensor | None = None,

@@ -192,6 +192,35 @@ int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k
 int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
                         int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream);
 
+/* The quantized gather (reduce_q with gather_format): the all-gather of the new theta is replaced
+ * by an all-gather of each owner's quantized update, same wire format, and every rank adds the same
+ * dequantized update to its replica.
+ *
+ * Phase 2' over one owned shard of n elements (n % 512 == 0): edt_sgd_apply_sum_q's sum and SGD
+ * update in registers,
+ *   a = round_g(((D(p_0) + D(p_1)) + ...) + D(p_{nacc-1})), grad = -a, SGD -> theta' and the momentum
+ * (the momentum is stored, bit-identical to edt_sgd_apply_sum_q's), then
+ *   u = f32(theta') - f32(theta)            one fp32 subtract
+ *   u' = u + residual                       one fp32 add, only with residual (error feedback)
+ *   q = Q(u') in fmt_out -> packed_out      one region of n elements, [payload | scales]
+ *   residual = u' - D(q)                    one fp32 subtract
+ * theta_g is NOT written. residual (nullable, n floats) is the owner's error feedback, sharded like
+ * the momentum. fmt_in (the regions') and fmt_out are independent. A non-finite update block
+ * stores scale byte 255. EDT_ERR_ARG for an unknown format, nacc outside [1, 64], n % 512 != 0, a
+ * bad dtype, a null buffer or an operand that is not 16-byte aligned. */
+int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in, void* momentum,
+                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, float* residual,
+                        void* packed_out, int fmt_out, void* stream);
+
+/* Phase 3 over a bucket of n elements: theta = round_g(f32(theta) + D(q)), one fp32 add then RNE to
+ * theta's dtype. `packed` holds n / region_elems regions back to back, each of region_elems
+ * elements ([src rank][payload | scales]: the mirror of edt_delta_partial_q's layout). The same call
+ * with the same bytes on every rank keeps the replicas bit-identical; a block with scale byte 255
+ * makes its 32 elements NaN. EDT_ERR_ARG when n % region_elems != 0, region_elems % 512 != 0, fmt
+ * or gdt is unknown, or an operand is null or not 16-byte aligned. */
+int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
+                      void* stream);
+
 /* ---- EDT pairwise merge -------------------------------------------------------------------
  * Replaces EDT_LM/train/crossover.py:150-163 + 166-230 for one child:
  *   B = lerp(0.5, b1, b2)                         (run_linear_merge_5050, in the model dtype wdt)

@@ -11,6 +11,15 @@ launches; medians over --steps steps after --warmup. The baseline runs three tim
 (first, middle, last), and its spread is recorded beside the numbers it judges.
 
     python scripts/reduce_q_probe.py --out profiles/reduce_q_probe.json
+
+--gather-format mxfp8|mxfp4 probes the quantized gather instead (reduce_q with gather_format): per
+group and error-feedback setting, plain reduce_q and the gather form alternate in this process on
+the same operands (plain, gather, plain, gather, plain), each kernel timed — phase 1
+(edt_delta_partial_q), phase 2 / 2' (edt_sgd_apply_sum_q / edt_sgd_delta_sum_q) and phase 3
+(edt_apply_delta_q) — and the result goes to profiles/gather_q_probe.json. The loopback's uint8
+all-gather fills every slot with this rank's own region, so phase 3 reads real blocks.
+
+    python scripts/reduce_q_probe.py --gather-format mxfp8
 """
 from __future__ import annotations
 
@@ -45,22 +54,27 @@ def loopback(world: int):
             return _Done()
 
         def all_gather(self, out, inp, async_op=False):
+            if out.dtype == torch.uint8 and world > 1:       # the quantized gather: every owner's region
+                out.view(world, -1)[1:].copy_(inp.expand(world - 1, -1))
             return _Done()
 
     return Loopback()
 
 
-def measure(layout, wdt, world, mode, fmt, ef, steps, warmup, dev, seed=0):
+def measure(layout, wdt, world, mode, fmt, ef, steps, warmup, dev, seed=0, gather=None):
     from evolutionarydistributedtraining_amd.distributed import ShardedOuterSync
     k_local = 8 // world
     s = ShardedOuterSync(layout, torch.float32, wdt, k_local, dev, mode=mode, broadcast="theta", comm=loopback(world),
-                         **({"wire_format": fmt, "error_feedback": ef} if mode == "reduce_q" else {}))
+                         **({"wire_format": fmt, "error_feedback": ef} if mode == "reduce_q" else {}),
+                         **({"gather_format": gather} if gather else {}))
     g = torch.Generator(device=dev).manual_seed(seed)
     s.theta_buf.normal_(0, 0.02, generator=g)
     for w in s.worker_bufs:
         w.copy_(s.theta_buf)
         w.add_(torch.randn(s.n_pad, device=dev, generator=g).mul_(1e-3))
     nb = len(s.buckets)
+    if gather:
+        return measure_gather(s, nb, fmt, ef, gather, steps, warmup)
     p1, p2 = [], []
     for i in range(warmup + steps):
         s.kernel_events = []
@@ -84,17 +98,102 @@ def measure(layout, wdt, world, mode, fmt, ef, steps, warmup, dev, seed=0):
     return out
 
 
+def measure_gather(s, nb, fmt, ef, gather, steps, warmup):
+    """The gather form's three phases per kernel, with each phase's algorithmic bytes."""
+    p1, p2, p3 = [], [], []
+    for i in range(warmup + steps):
+        s.kernel_events = []
+        s.step()
+        torch.cuda.synchronize()
+        ms = [a.elapsed_time(b) for a, b in s.kernel_events]
+        assert len(ms) == 3 * nb
+        if i >= warmup:
+            p1.append(sum(ms[:nb]))
+            p2.append(sum(ms[nb:2 * nb]))
+            p3.append(sum(ms[2 * nb:]))
+    tot = [a + b + c for a, b, c in zip(p1, p2, p3)]
+    shard = s.n_pad // s.world
+    e8 = 8 if ef else 0
+    b2 = shard * (4 + 8 + e8) + s.world * s._q_bytes(shard) + s._q_bytes(shard, gather)
+    b3 = s.n_pad * 8 + s._q_bytes(s.n_pad, gather)
+    kb = s.kernel_bytes()
+    m2, m3 = statistics.median(p2), statistics.median(p3)
+    out = {"mode": "reduce_q", "wire_format": fmt, "gather_format": gather, "error_feedback": ef, "buckets": nb,
+           "n_pad": s.n_pad, "phase1_ms": round(statistics.median(p1), 4), "phase2_ms": round(m2, 4),
+           "phase3_ms": round(m3, 4), "ms": round(statistics.median(tot), 4), "kernel_bytes": kb,
+           "phase2_bytes": b2, "phase3_bytes": b3,
+           "phase2_fraction_of_8TBps": round(b2 / m2 / PEAK_BYTES_PER_MS, 4),
+           "phase3_fraction_of_8TBps": round(b3 / m3 / PEAK_BYTES_PER_MS, 4),
+           "fraction_of_8TBps": round(kb / statistics.median(tot) / PEAK_BYTES_PER_MS, 4),
+           "wire_bytes_computed": s.wire_bytes()}
+    del s
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+def gather_main(a, layout, dev):
+    from evolutionarydistributedtraining_amd import _lib as L
+    gf, fmt = a.gather_format, "mxfp8"
+    groups = []
+    for world in (1, 8):
+        for name, wdt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+            for ef in (False, True):
+                run = lambda g=None: measure(layout, wdt, world, "reduce_q", fmt, ef, a.steps, a.warmup, dev, gather=g)
+                runs = [run(), run(gf), run(), run(gf), run()]
+                plain, gath = runs[0::2], runs[1::2]
+                med = lambda rows, key: round(statistics.median(r[key] for r in rows), 4)
+                shard = plain[0]["n_pad"] // world
+                b2_plain = shard * (8 + 8) + world * (shard + shard // 32)
+                p2 = med(plain, "phase2_ms")
+                # what phase 2' + phase 3 would cost if their bytes moved at the rate the same run's
+                # plain phase 2 achieves, against what they took
+                at_rate = (gath[0]["phase2_bytes"] + gath[0]["phase3_bytes"]) / (b2_plain / p2)
+                took = med(gath, "phase2_ms") + med(gath, "phase3_ms")
+                grp = {"world": world, "workers": name, "theta": "f32", "k_local": 8 // world, "error_feedback": ef,
+                       "reduce_q": dict(plain[1], phase1_ms=med(plain, "phase1_ms"), phase2_ms=p2, ms=med(plain, "ms"),
+                                        repeats_phase2_ms=[r["phase2_ms"] for r in plain],
+                                        repeats_ms=[r["ms"] for r in plain], phase2_bytes=b2_plain,
+                                        phase2_fraction_of_8TBps=round(b2_plain / p2 / PEAK_BYTES_PER_MS, 4),
+                                        spread_ms=round(max(r["ms"] for r in plain) - min(r["ms"] for r in plain), 4)),
+                       "gather_q": dict(gath[0], phase1_ms=med(gath, "phase1_ms"), phase2_ms=med(gath, "phase2_ms"),
+                                        phase3_ms=med(gath, "phase3_ms"), ms=med(gath, "ms"),
+                                        repeats_ms=[r["ms"] for r in gath]),
+                       "phase2p_plus_phase3_ms": round(took, 4),
+                       "same_bytes_at_plain_phase2_rate_ms": round(at_rate, 4),
+                       "ratio_to_plain_phase2_rate": round(took / at_rate, 4),
+                       "extra_local_ms_over_reduce_q": round(med(gath, "ms") - med(plain, "ms"), 4)}
+                groups.append(grp)
+                print(json.dumps(grp), flush=True)
+    res = {"probe": "gather_q_probe", "layout": a.layout, "elements": layout.total, "K": 8, "steps": a.steps,
+           "warmup": a.warmup, "wire_format": fmt, "gather_format": gf, "device": torch.cuda.get_device_name(0),
+           "library_sha256": L.library_sha256(),
+           "note": "local kernels only, one GPU, loopback communicator; wire_bytes_computed follow from the byte "
+                   "counts and were not measured on a multi-GPU node", "groups": groups}
+    out = a.out or os.path.join(ROOT, "profiles", "gather_q_probe.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--layout", default="gpt_1p3b")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reduce_q_probe.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/reduce_q_probe.json (gather_q_probe.json "
+                                                "with --gather-format)")
+    ap.add_argument("--gather-format", choices=("mxfp8", "mxfp4"), default=None,
+                    help="probe the quantized gather next to plain reduce_q instead")
     a = ap.parse_args()
     from evolutionarydistributedtraining_amd import _lib as L
     from evolutionarydistributedtraining_amd.layouts import LAYOUTS
     dev = torch.device("cuda:0")
     layout = LAYOUTS[a.layout]()
+    if a.gather_format:
+        return gather_main(a, layout, dev)
+    a.out = a.out or os.path.join(ROOT, "profiles", "reduce_q_probe.json")
     groups = []
     for world in (1, 8):
         for name, wdt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
