@@ -20,6 +20,8 @@ EDT_BF16 = 1
 EDT_MAX_WORKERS = 64
 EDT_MXFP8 = 0               # edt_qfmt_t: the wire formats of the quantized partial exchange
 EDT_MXFP4 = 1
+EDT_ROUND_NEAREST = 0       # edt_round_t: how the quantizing encoders pick the grid neighbour
+EDT_ROUND_STOCHASTIC = 1
 EDT_ABI_VERSION = 6         # include/edt_sync.h: the revision these signatures and workspace sizes follow
 
 _DT = {torch.float32: EDT_F32, torch.bfloat16: EDT_BF16}
@@ -49,6 +51,10 @@ SIGNATURES = [
     ("edt_sgd_apply_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_sgd_delta_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _P, _I, _P]),
     ("edt_apply_delta_q", _I, [_P, _I, _P, _U64, _U64, _I, _P]),
+    ("edt_delta_partial_q_sr", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _U64, _I, _P, _U64, _U64,
+                                    ctypes.c_uint32, _U64, _P]),
+    ("edt_sgd_delta_sum_q_sr", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _I, _U64, _U64,
+                                    ctypes.c_uint32, _U64, _P]),
     ("edt_pair_merge", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_to", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_population", _I, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),

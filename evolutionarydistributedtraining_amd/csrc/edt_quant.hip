@@ -23,6 +23,19 @@
 //   D(q)      elem * 2^e, exact in fp32
 //   fp32 subnormal inputs are outside the bit-exact contract (finite, within one grid step).
 //
+// Stochastic rounding (EDT_ROUND_STOCHASTIC, the *_sr entries; tests/sr_reference.py restates it):
+// blocks, packing, layout, the non-finite rule and D(q) as above; the encoder differs in
+//   scale     e as above, then e + 1 when amax * 2^-e exceeds the element maximum (448 / 6), so no
+//             finite element saturates; byte = clamp(e + 127, 0, 254)
+//   elements  a = |v| 2^-e, k = max(floor(log2 a), EMIN), q = 2^(k - MB), t = a / q, lo = floor(t),
+//             f16 = floor((t - lo) 2^16): the element is (lo + up) q, up = (r16 < f16); the sign is kept
+//   r16       Philox4x32-10 (kPhiloxRounds) keyed by the 64-bit seed at counter (g lo, g hi, step,
+//             stream), g = global element index / 8 — the lane's 8 elements; element 8g + j takes bits
+//             16 (j % 2) .. + 15 of output word j / 2
+// Here floor(t 2^16) = lo 2^16 + f16 is one exact fp32 multiply and a truncating convert, and adding
+// 0xffff - r16 to it carries into bit 16 exactly when r16 < f16; the magnitude code is then
+// ((k - EMIN) << MB) + lo + up for normal and subnormal elements alike (EMIN + BIAS = 1 in both formats).
+//
 // Mapping: a thread owns 8 consecutive elements (one 16-byte load per bf16 operand, two per fp32
 // operand), so 4 adjacent lanes hold a block: the block amax is a two-step xor butterfly, a wave
 // covers 512 elements = 16 blocks, and sizes are multiples of 512 so every wave is whole. Payload
@@ -63,6 +76,31 @@ template <> struct QFmt<EDT_MXFP4> {
 
 __device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }   // -126 <= e <= 127
 
+// stochastic rounding: the Philox key (the seed) and what of the counter is the same for a whole call
+struct QSr {
+    uint32_t key0, key1;     // seed, low and high word
+    uint32_t step;           // counter word 2
+    uint32_t stream;         // counter word 3
+    uint64_t group_base;     // elem_base / 8: the call's first group of 8 elements
+};
+
+constexpr int kPhiloxRounds = EDT_PHILOX_ROUNDS;
+
+// Philox4x32 (Salmon et al., SC'11), kPhiloxRounds rounds: counter c, key (k0, k1) -> c
+__device__ __forceinline__ void philox4x32(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < kPhiloxRounds; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0;
+        c[1] = (uint32_t)p1;
+        c[2] = n2;
+        c[3] = (uint32_t)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
 // |x| (finite, < 2^(EMAX + 1)) rounded to nearest-even onto the element grid and saturated:
 // adding 2^23 q, q the grid step at |x|, makes the fp32 adder round at q.
 template <int FMT>
@@ -95,11 +133,14 @@ __device__ __forceinline__ float q_decode(uint32_t c) {
 // The quantize-and-store tail shared by phase 1 and phase 2': the 8 values v at element `off` of the
 // region at `base` (off a multiple of 8; the wave's 64 lanes cover 512 consecutive elements of one
 // region) become codes under their block's scale; with EF the residual v - D(q) goes to res[i].
-template <int FMT, bool EF>
+// RND = EDT_ROUND_STOCHASTIC (never with EF): the bumped scale and the Philox draw of group
+// sr.group_base + i / 8 (i: the element's index inside the call) pick the grid neighbour.
+template <int FMT, bool EF, int RND = EDT_ROUND_NEAREST>
 __device__ __forceinline__ void quant_store(const float (&acc)[kVec], float* res, uint64_t i, uint8_t* base,
-                                            uint64_t off, uint64_t payload_bytes) {
+                                            uint64_t off, uint64_t payload_bytes, const QSr& sr = QSr{}) {
     using F = QFmt<FMT>;
     constexpr int N = kVec;
+    static_assert(!(EF && RND == EDT_ROUND_STOCHASTIC), "stochastic rounding takes no residual");
     // block amax over the bit patterns of |v| (monotone for finite values; NaN / Inf compare highest)
     uint32_t m = 0;
 #pragma unroll
@@ -113,6 +154,8 @@ __device__ __forceinline__ void quant_store(const float (&acc)[kVec], float* res
     m = o > m ? o : m;
     const bool bad = m >= 0x7f800000u;
     int sb = (int)(m >> 23) - F::EMAX;                   // e + 127
+    if constexpr (RND == EDT_ROUND_STOCHASTIC)           // amax * 2^-e > MAXV: the mantissa decides
+        sb += (m & 0x7fffffu) > (__float_as_uint(F::MAXV) & 0x7fffffu) ? 1 : 0;
     sb = sb < 0 ? 0 : sb;
     if (bad) sb = 255;
     // v * 2^-e = v * 2^(127 - sb): one exact multiply; back by 2^e as two exact factors, since
@@ -122,13 +165,32 @@ __device__ __forceinline__ void quant_store(const float (&acc)[kVec], float* res
     const float d0 = pow2f(up > 64 ? -64 : -up), d1 = pow2f(up > 64 ? 64 - up : 0);
     uint32_t code[N];
     float deq[N];
+    if constexpr (RND == EDT_ROUND_STOCHASTIC) {
+        const uint64_t g = sr.group_base + (i >> 3);
+        uint32_t w[4] = {(uint32_t)g, (uint32_t)(g >> 32), sr.step, sr.stream};
+        philox4x32(w, sr.key0, sr.key1);
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const uint32_t sign = __float_as_uint(acc[j]) & 0x80000000u;
-        const float ax = __uint_as_float(__float_as_uint(acc[j]) & 0x7fffffffu) * su;
-        const float r = q_round<FMT>(bad ? 0.f : ax);
-        code[j] = bad ? 0u : (q_code<FMT>(r) | (sign >> (32 - F::BITS)));
-        deq[j] = bad ? __builtin_nanf("") : __uint_as_float(__float_as_uint(r * d0 * d1) | sign);   // D(q)
+        for (int j = 0; j < N; ++j) {
+            const uint32_t nr = j & 1 ? ~w[j >> 1] >> 16 : ~w[j >> 1] & 0xffffu;     // 0xffff - r16
+            const uint32_t sign = __float_as_uint(acc[j]) & 0x80000000u;
+            float ax = __uint_as_float(__float_as_uint(acc[j]) & 0x7fffffffu) * su;
+            ax = bad ? 0.f : ax;
+            uint32_t kb = __float_as_uint(ax) >> 23;                                  // k + 127
+            kb = kb < (uint32_t)(F::EMIN + 127) ? (uint32_t)(F::EMIN + 127) : kb;
+            // floor(t 2^16), t = a 2^(MB - k) < 2^(MB + 1): exact product, truncating convert
+            const uint32_t fx = (uint32_t)(ax * __uint_as_float(((uint32_t)(2 * 127 + F::MB + 16) - kb) << 23));
+            const uint32_t mag = ((kb - (uint32_t)(F::EMIN + 127)) << F::MB) + ((fx + nr) >> 16);
+            code[j] = bad ? 0u : (mag | (sign >> (32 - F::BITS)));
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const uint32_t sign = __float_as_uint(acc[j]) & 0x80000000u;
+            const float ax = __uint_as_float(__float_as_uint(acc[j]) & 0x7fffffffu) * su;
+            const float r = q_round<FMT>(bad ? 0.f : ax);
+            code[j] = bad ? 0u : (q_code<FMT>(r) | (sign >> (32 - F::BITS)));
+            deq[j] = bad ? __builtin_nanf("") : __uint_as_float(__float_as_uint(r * d0 * d1) | sign);   // D(q)
+        }
     }
     if constexpr (EF) {
         float r[N];
@@ -157,8 +219,8 @@ __device__ __forceinline__ void quant_store(const float (&acc)[kVec], float* res
 }
 
 // Phase 1 for the 8 elements at i (a multiple of 8; the wave's 64 lanes cover 512 consecutive ones).
-template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
-__device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t i) {
+template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF, int RND = EDT_ROUND_NEAREST>
+__device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t i, const QSr& sr = QSr{}) {
     constexpr int N = kVec;
     float g[N], acc[N];
     ld<GDT, N, (EDT_NT_RMW != 0)>(a.theta, i, g);
@@ -203,7 +265,7 @@ __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t 
     else reg = (uint32_t)tile / (uint32_t)a.tiles_per_region;
     const uint64_t off = i - reg * (a.tiles_per_region << 9);        // element offset inside the region
     uint8_t* base = a.packed + reg * a.region_bytes;
-    quant_store<FMT, EF>(acc, a.residual, i, base, off, a.payload_bytes);
+    quant_store<FMT, EF, RND>(acc, a.residual, i, base, off, a.payload_bytes, sr);
 }
 
 template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
@@ -212,6 +274,15 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_kernel(
     const uint64_t nv = a.n / kVec;                      // n % 512 == 0: a wave is in or out as a whole
     for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride)
         partial_q_elems<GDT, WDT, KC, DIV, FMT, EF>(a, v * kVec);
+}
+
+// phase 1 with stochastic rounding: the same partial, no residual, the draw of each lane's group
+template <int GDT, int WDT, int KC, int DIV, int FMT>
+__global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_sr_kernel(QPartialArgs a, QSr sr) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t nv = a.n / kVec;
+    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride)
+        partial_q_elems<GDT, WDT, KC, DIV, FMT, false, EDT_ROUND_STOCHASTIC>(a, v * kVec, sr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -308,6 +379,38 @@ __global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_kernel(const void* the
     }
 }
 
+// phase 2' with stochastic rounding of the update: sgd_delta_sum_q_kernel's step without a residual
+// (the nearest kernel above keeps its own text, so its code stays what it was)
+template <int GDT, int FIN, int FOUT>
+__global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_sr_kernel(const void* theta, QRegions P, int np, void* mom,
+                                                                    uint64_t n, SgdScalars s, uint8_t* packed_out,
+                                                                    QSr sr) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t nv = n / kVec;
+    const uint64_t payload = n / 8 * QFmt<FOUT>::BITS;
+    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
+        const uint64_t i = v * kVec;
+        float g0[kVec], g[kVec], a[kVec], grad[kVec], b_in[kVec];
+        ld<GDT, kVec>(theta, i, g0);
+        ld_momentum<GDT, kVec>(mom, i, s, b_in);
+        ld_q<FIN>(P.p[0], n, i, a);
+        for (int r = 1; r < np; ++r) {
+            float x[kVec];
+            ld_q<FIN>(P.p[r], n, i, x);
+#pragma unroll
+            for (int j = 0; j < kVec; ++j) a[j] = a[j] + x[j];
+        }
+        rnd<GDT>(a);
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) { grad[j] = -a[j]; g[j] = g0[j]; }
+        sgd_update<GDT, kVec>(g, grad, mom, i, s, b_in);
+        float u[kVec];
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) u[j] = g[j] - g0[j];
+        quant_store<FOUT, false, EDT_ROUND_STOCHASTIC>(u, nullptr, i, packed_out, i, payload, sr);
+    }
+}
+
 // phase 3: theta <- round_g(theta + D(q)) over a bucket of n / region_elems regions back to back
 template <int GDT, int FMT>
 __global__ __launch_bounds__(kBlock) void apply_delta_q_kernel(void* theta, const uint8_t* packed, uint64_t n,
@@ -354,6 +457,45 @@ int launch_partial_q(const QPartialArgs& a, int fmt, bool div_exact, hipStream_t
                       : launch_partial_q_k<GDT, WDT, EDT_MXFP4, false>(a, div_exact, s);
 }
 
+template <int GDT, int WDT, int FMT>
+int launch_partial_q_sr_k(const QPartialArgs& a, const QSr& sr, bool div_exact, hipStream_t s) {
+    const unsigned g = grid_for(a.n, true);
+    if (a.K == 8 && !div_exact) delta_partial_q_sr_kernel<GDT, WDT, 8, 0, FMT><<<g, kBlock, 0, s>>>(a, sr);
+    else if (div_exact) delta_partial_q_sr_kernel<GDT, WDT, 0, 1, FMT><<<g, kBlock, 0, s>>>(a, sr);
+    else delta_partial_q_sr_kernel<GDT, WDT, 0, 0, FMT><<<g, kBlock, 0, s>>>(a, sr);
+    return check_launch("delta_partial_q_sr_kernel");
+}
+
+template <int GDT, int WDT>
+int launch_partial_q_sr(const QPartialArgs& a, const QSr& sr, int fmt, bool div_exact, hipStream_t s) {
+    if (fmt == EDT_MXFP8) return launch_partial_q_sr_k<GDT, WDT, EDT_MXFP8>(a, sr, div_exact, s);
+    return launch_partial_q_sr_k<GDT, WDT, EDT_MXFP4>(a, sr, div_exact, s);
+}
+
+template <int GDT>
+void launch_delta_sum_q_sr(const void* theta, const QRegions& P, int np, int fmt_in, void* mom, uint64_t n,
+                           const SgdScalars& sc, uint8_t* out, int fmt_out, const QSr& sr, hipStream_t s) {
+    const unsigned g = grid_for(n, true);
+    if (fmt_in == EDT_MXFP8 && fmt_out == EDT_MXFP8)
+        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP8, EDT_MXFP8><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
+    else if (fmt_in == EDT_MXFP8)
+        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP8, EDT_MXFP4><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
+    else if (fmt_out == EDT_MXFP8)
+        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP4, EDT_MXFP8><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
+    else
+        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP4, EDT_MXFP4><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
+}
+
+inline QSr make_sr(uint64_t seed, uint64_t step, uint32_t stream_id, uint64_t elem_base) {
+    QSr sr;
+    sr.key0 = (uint32_t)seed;
+    sr.key1 = (uint32_t)(seed >> 32);
+    sr.step = (uint32_t)step;
+    sr.stream = stream_id;
+    sr.group_base = elem_base / 8;
+    return sr;
+}
+
 template <int GDT, int FIN, int FOUT>
 void launch_delta_sum_q_e(const void* theta, const QRegions& P, int np, void* mom, uint64_t n, const SgdScalars& sc,
                           float* residual, uint8_t* out, hipStream_t s) {
@@ -385,9 +527,10 @@ uint64_t edt_q_region_bytes(uint64_t region_elems, int fmt) {
     return region_elems / 8 * bits + region_elems / 32;
 }
 
-int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
-                        int K_total, uint64_t n, uint64_t region_elems, int fmt, float* residual, void* packed,
-                        void* stream) {
+// edt_delta_partial_q (sr null) and edt_delta_partial_q_sr: one validation, one argument block
+static int delta_partial_q_impl(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                                int K_total, uint64_t n, uint64_t region_elems, int fmt, float* residual, void* packed,
+                                const QSr* sr, uint64_t elem_base, void* stream) {
     g_err[0] = 0;
     if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
     if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
@@ -399,6 +542,9 @@ int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k
     if (n % region_elems)
         return fail(EDT_ERR_ARG, "n = %llu is not a whole number of regions of %llu elements", (unsigned long long)n,
                     (unsigned long long)region_elems);
+    if (elem_base % 8)
+        return fail(EDT_ERR_ARG, "elem_base %llu is not a multiple of 8 (one lane's group of elements)",
+                    (unsigned long long)elem_base);
     if (!theta_k) return fail(EDT_ERR_ARG, "theta_k is null");
     if (n == 0) return EDT_OK;
     if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
@@ -424,9 +570,29 @@ int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k
     a.kinv = 1.0f / (float)K_total;
     const bool div_exact = !is_pow2(K_total);
     hipStream_t s = (hipStream_t)stream;
+    if (sr) {
+        if (gdt == EDT_F32 && wdt == EDT_F32) return launch_partial_q_sr<EDT_F32, EDT_F32>(a, *sr, fmt, div_exact, s);
+        if (gdt == EDT_F32) return launch_partial_q_sr<EDT_F32, EDT_BF16>(a, *sr, fmt, div_exact, s);
+        return launch_partial_q_sr<EDT_BF16, EDT_BF16>(a, *sr, fmt, div_exact, s);
+    }
     if (gdt == EDT_F32 && wdt == EDT_F32) return launch_partial_q<EDT_F32, EDT_F32>(a, fmt, div_exact, s);
     if (gdt == EDT_F32) return launch_partial_q<EDT_F32, EDT_BF16>(a, fmt, div_exact, s);
     return launch_partial_q<EDT_BF16, EDT_BF16>(a, fmt, div_exact, s);
+}
+
+int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                        int K_total, uint64_t n, uint64_t region_elems, int fmt, float* residual, void* packed,
+                        void* stream) {
+    return delta_partial_q_impl(theta_g, gdt, theta_k, wdt, K_local, K_total, n, region_elems, fmt, residual, packed,
+                                nullptr, 0, stream);
+}
+
+int edt_delta_partial_q_sr(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                           int K_total, uint64_t n, uint64_t region_elems, int fmt, void* packed, uint64_t seed,
+                           uint64_t step, uint32_t stream_id, uint64_t elem_base, void* stream) {
+    const QSr sr = make_sr(seed, step, stream_id, elem_base);
+    return delta_partial_q_impl(theta_g, gdt, theta_k, wdt, K_local, K_total, n, region_elems, fmt, nullptr, packed,
+                                &sr, elem_base, stream);
 }
 
 int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
@@ -462,9 +628,11 @@ int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int 
     return check_launch("sgd_apply_sum_q_kernel");
 }
 
-int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in, void* momentum,
-                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, float* residual,
-                        void* packed_out, int fmt_out, void* stream) {
+// edt_sgd_delta_sum_q (sr null) and edt_sgd_delta_sum_q_sr
+static int sgd_delta_sum_q_impl(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
+                                void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
+                                int nesterov, float* residual, void* packed_out, int fmt_out, const QSr* sr,
+                                uint64_t elem_base, void* stream) {
     g_err[0] = 0;
     if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
     if (!fmt_bits(fmt_in)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt_in);
@@ -472,6 +640,9 @@ int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions
     if (nacc < 1 || nacc > EDT_MAX_WORKERS)
         return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc, EDT_MAX_WORKERS);
     if (n % 512) return fail(EDT_ERR_ARG, "n = %llu is not a multiple of 512 (one region)", (unsigned long long)n);
+    if (elem_base % 8)
+        return fail(EDT_ERR_ARG, "elem_base %llu is not a multiple of 8 (one lane's group of elements)",
+                    (unsigned long long)elem_base);
     if (n == 0) return EDT_OK;
     if (!theta_g || !regions) return fail(EDT_ERR_ARG, "null buffer");
     if (!packed_out) return fail(EDT_ERR_ARG, "packed_out is null");
@@ -488,9 +659,30 @@ int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions
     if (!al) return fail(EDT_ERR_ARG, "the quantized update needs 16-byte aligned operands");
     hipStream_t st = (hipStream_t)stream;
     uint8_t* out = static_cast<uint8_t*>(packed_out);
+    if (sr) {
+        if (gdt == EDT_F32) launch_delta_sum_q_sr<EDT_F32>(theta_g, P, nacc, fmt_in, momentum, n, s, out, fmt_out, *sr, st);
+        else launch_delta_sum_q_sr<EDT_BF16>(theta_g, P, nacc, fmt_in, momentum, n, s, out, fmt_out, *sr, st);
+        return check_launch("sgd_delta_sum_q_sr_kernel");
+    }
     if (gdt == EDT_F32) launch_delta_sum_q<EDT_F32>(theta_g, P, nacc, fmt_in, momentum, n, s, residual, out, fmt_out, st);
     else launch_delta_sum_q<EDT_BF16>(theta_g, P, nacc, fmt_in, momentum, n, s, residual, out, fmt_out, st);
     return check_launch("sgd_delta_sum_q_kernel");
+}
+
+int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in, void* momentum,
+                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, float* residual,
+                        void* packed_out, int fmt_out, void* stream) {
+    return sgd_delta_sum_q_impl(theta_g, gdt, regions, nacc, fmt_in, momentum, has_momentum, n, lr, momentum_coef,
+                                nesterov, residual, packed_out, fmt_out, nullptr, 0, stream);
+}
+
+int edt_sgd_delta_sum_q_sr(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
+                           void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                           void* packed_out, int fmt_out, uint64_t seed, uint64_t step, uint32_t stream_id,
+                           uint64_t elem_base, void* stream) {
+    const QSr sr = make_sr(seed, step, stream_id, elem_base);
+    return sgd_delta_sum_q_impl(theta_g, gdt, regions, nacc, fmt_in, momentum, has_momentum, n, lr, momentum_coef,
+                                nesterov, nullptr, packed_out, fmt_out, &sr, elem_base, stream);
 }
 
 int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,

@@ -38,6 +38,12 @@ on the comm stream overlaps the HBM-bound kernels on the compute stream:
                          u' = u + r_g, r_g = u' - D(Q(u'))). Wire bytes: (N-1)/N * P * (q_in + q_out)
                          — 2.0625 B/elem with mxfp8 both ways whatever theta's dtype; computed from
                          the byte counts, not measured on a multi-GPU node.
+    rounding="stochastic" (reduce_q only, opt-in, instead of error feedback) makes both encoders
+                         round each element to one of its two grid neighbours with the probability
+                         of its distance (Philox4x32-10 bits from `seed`, the step counter
+                         `q_step`, a stream per rank and encoder, and the element's index in the
+                         arena): unbiased in expectation, no residual buffers, no extra HBM bytes.
+                         The decoders and the bytes' layout are unchanged.
   mode="exact"           all-to-all of the raw worker shards to their owners, then the single-GPU
                          fused kernel on each shard (the reference's worker order, bit-exact),
                          all-gather of theta. Wire bytes: (N-1)/N * P * (K_local * b_w + b_g).
@@ -82,7 +88,8 @@ class ShardedOuterSync:
                  mode: str = "auto", bucket_elems: int = 1 << 26, group=None, kernels=None,
                  broadcast: str = "auto", comm: Collectives | None = None,
                  cpu_tails: tuple[int, int] | None = None, wire_format: str = "mxfp8",
-                 error_feedback: bool = True, gather_format: str | None = None):
+                 error_feedback: bool = True, gather_format: str | None = None, rounding: str = "nearest",
+                 seed: int = 0):
         """mode="reduce_q": `wire_format` picks the element format of the quantized partials and
         `error_feedback` keeps `self.residual` — this rank's fp32 quantization error (n_pad
         elements), added to the next step's partial before it is quantized. The residual is per
@@ -90,7 +97,12 @@ class ShardedOuterSync:
         restart without it loses at most one step's quantization error. `gather_format` (reduce_q
         only) ships the owners' quantized updates instead of theta (module docstring); with
         error_feedback it keeps `self.residual_g`, the owner's fp32 error of that quantization
-        (sharded like the momentum), under the same restart rule."""
+        (sharded like the momentum), under the same restart rule. `rounding="stochastic"` (reduce_q
+        with error_feedback=False only) rounds stochastically instead and keeps no residual: its
+        whole state is `seed` and the public integer `q_step`, which starts at 0, numbers the
+        current step's random bits and is incremented at the end of step(). q_step is settable: a
+        restart that restores it (with theta, the momentum and the same seed) replays the same
+        bits, so the run continues bit for bit."""
         if (mode not in ("reduce", "reduce_ordered", "reduce_q", "exact", "auto")
                 or broadcast not in ("theta", "workers", "auto")):
             raise ValueError((mode, broadcast))
@@ -103,6 +115,15 @@ class ShardedOuterSync:
                 raise ValueError("gather_format quantizes the gather of mode='reduce_q' only")
             if gather_format not in _Q_BITS:
                 raise ValueError(f"gather_format {gather_format!r}: None, 'mxfp8' or 'mxfp4'")
+        if rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"rounding {rounding!r}: 'nearest' or 'stochastic'")
+        if rounding == "stochastic":
+            if mode != "reduce_q":
+                raise ValueError(f"rounding='stochastic' needs mode='reduce_q' (the quantizing schedule), not mode={mode!r}")
+            if error_feedback:
+                raise ValueError("rounding='stochastic' needs error_feedback=False: it replaces the residual")
+            if not 0 <= int(seed) < 1 << 64:
+                raise ValueError(f"seed {seed!r}: an unsigned 64-bit integer")
         check_sgd_hparams(lr, momentum, nesterov)
         # the communicator seam: torch.distributed (RCCL / gloo) by default, or N virtual ranks
         # on one device (collectives.VirtualWorld)
@@ -128,6 +149,8 @@ class ShardedOuterSync:
         self.lr, self.momentum, self.nesterov = lr, momentum, nesterov
         self.k_local = k_local
         self.k_total = k_local * self.world
+        self.rounding, self.seed = rounding, int(seed)
+        self.q_step = 0                # stochastic rounding: the step counter of the random bits
         n = layout.total
         # buckets: multiples of world * 64 elements so every shard is 16-byte aligned (reduce_q:
         # world * 512, so every shard is a whole region of the wire format)
@@ -191,14 +214,14 @@ class ShardedOuterSync:
         byte offset of element offset `elems` in the send / receive buffers."""
         return elems * _Q_BITS[fmt or self.wire_format] // 8 + elems // 32
 
-    def _launch(self, fn, *args):
+    def _launch(self, fn, *args, **kw):
         """A local kernel, bracketed by timing events on its launch stream when
         `kernel_events` is a list (bench.py: the per-rank HBM roofline at N > 1)."""
         if self.kernel_events is None:
-            return fn(*args)
+            return fn(*args, **kw)
         a, b = self.event_factory(), self.event_factory()
         a.record()
-        fn(*args)
+        fn(*args, **kw)
         b.record()
         self.kernel_events.append((a, b))
 
@@ -234,6 +257,16 @@ class ShardedOuterSync:
         """One outer step; returns when the work is enqueued (stream-ordered, async)."""
         with trange(f"edt/sharded.{self.mode}/{self.broadcast}"):
             self._step_body()
+        self.q_step += 1
+
+    def _sr(self, encoder: int, elem_base: int) -> dict:
+        """The stochastic-rounding keywords of one encoder launch (none in nearest mode, so stand-in
+        kernels without them keep working): stream 2 * rank for phase 1, 2 * rank + 1 for phase 2';
+        elem_base is the launch's first element in the arena."""
+        if self.rounding != "stochastic":
+            return {}
+        return {"rounding": "stochastic", "seed": self.seed, "step": self.q_step,
+                "stream_id": 2 * self.rank + encoder, "elem_base": elem_base}
 
     def _step_body(self) -> None:
         k = self.kernels
@@ -284,7 +317,7 @@ class ShardedOuterSync:
                 qb, qe = self._q_bytes(b), self._q_bytes(e)
                 self._launch(k.delta_partial_q, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
                              self.k_total, self.q_send[qb:qe], per, self.wire_format,
-                             None if self.residual is None else self.residual[b:e])
+                             None if self.residual is None else self.residual[b:e], **self._sr(0, b))
                 works.append(self.comm.all_to_all(self.q_recv[qb:qe], self.q_send[qb:qe], async_op=True))
             # phase 2: the owned shard's N regions dequantized, summed in rank order + SGD
             for (b, e), w in zip(self.buckets, works):
@@ -305,7 +338,8 @@ class ShardedOuterSync:
                     slot = self.u_recv[ub + self.rank * ur:ub + (self.rank + 1) * ur]
                     res_g = None if self.residual_g is None else self.residual_g[mom_off:mom_off + per]
                     self._launch(k.sgd_delta_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
-                                 self.has_momentum, self.lr, self.momentum, self.nesterov, slot, gf, res_g)
+                                 self.has_momentum, self.lr, self.momentum, self.nesterov, slot, gf, res_g,
+                                 **self._sr(1, s0))
                     src = slot if self.inplace else slot.clone()
                     gathers.append(self.comm.all_gather(self.u_recv[ub:self._q_bytes(e, gf)], src, async_op=True))
                 mom_off += per

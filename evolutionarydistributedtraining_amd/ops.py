@@ -207,13 +207,35 @@ def q_region_bytes(region_elems: int, fmt) -> int:
     return int(L.load_library().edt_q_region_bytes(int(region_elems), _qfmt(fmt)))
 
 
+ROUNDING = {"nearest": L.EDT_ROUND_NEAREST, "stochastic": L.EDT_ROUND_STOCHASTIC}
+
+
+def _stochastic(rounding, residual, seed, step, stream_id, elem_base) -> bool:
+    """Checks the rounding keywords of the two quantizing encoders; True for stochastic rounding."""
+    if rounding not in ROUNDING:
+        raise L.EdtError(f"unknown rounding {rounding!r}: 'nearest' or 'stochastic'")
+    if rounding == "nearest":
+        return False
+    if residual is not None:
+        raise L.EdtError("rounding='stochastic' takes no residual (it replaces error feedback)")
+    if not 0 <= int(seed) < 1 << 64 or not 0 <= int(step) < 1 << 64 or not 0 <= int(stream_id) < 1 << 32:
+        raise L.EdtError("seed and step are unsigned 64-bit, stream_id unsigned 32-bit")
+    if not 0 <= int(elem_base) < 1 << 64 or int(elem_base) % 8:
+        raise L.EdtError(f"elem_base {elem_base} is not a non-negative multiple of 8")
+    return True
+
+
 def delta_partial_q(theta: torch.Tensor, workers: list[torch.Tensor], k_total: int, packed: torch.Tensor,
-                    region_elems: int, fmt, residual: torch.Tensor | None = None) -> None:
+                    region_elems: int, fmt, residual: torch.Tensor | None = None, rounding: str = "nearest",
+                    seed: int = 0, step: int = 0, stream_id: int = 0, elem_base: int = 0) -> None:
     """delta_partial's fp32 partial, block-quantized (fmt: 'mxfp8' | 'mxfp4', include/edt_sync.h)
     into `packed` (uint8) as theta.numel() / region_elems regions back to back; the fp32 partial
     never reaches HBM. residual (fp32, theta's size): error feedback, added before and rewritten
-    after the quantization (edt_delta_partial_q)."""
+    after the quantization (edt_delta_partial_q). rounding='stochastic' (edt_delta_partial_q_sr, no
+    residual): element i draws the Philox bits of (seed, step, stream_id, global element
+    elem_base + i); elem_base is a multiple of 8."""
     lib = L.lib()
+    sr = _stochastic(rounding, residual, seed, step, stream_id, elem_base)
     if not workers:
         raise L.EdtError("no workers")
     L.require_device(theta, packed, residual, *workers)
@@ -228,6 +250,12 @@ def delta_partial_q(theta: torch.Tensor, workers: list[torch.Tensor], k_total: i
         raise L.EdtError("packed: a uint8 buffer of theta.numel() / region_elems regions of q_region_bytes each")
     if residual is not None and (residual.dtype != torch.float32 or residual.numel() != n):
         raise L.EdtError("residual must be a float32 buffer of theta's size")
+    if sr:
+        L.check(lib.edt_delta_partial_q_sr(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
+                                           L.dtype_code(workers[0]), len(workers), int(k_total), n, int(region_elems),
+                                           code, L.ptr(packed), int(seed), int(step), int(stream_id), int(elem_base),
+                                           L.stream_ptr(theta.device)), "edt_delta_partial_q_sr")
+        return
     L.check(lib.edt_delta_partial_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
                                     L.dtype_code(workers[0]), len(workers), int(k_total), n, int(region_elems), code,
                                     L.ptr(residual), L.ptr(packed), L.stream_ptr(theta.device)),
@@ -257,13 +285,17 @@ def sgd_apply_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt, momen
 
 def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, momentum: torch.Tensor | None,
                     has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool, packed_out: torch.Tensor,
-                    fmt_out, residual: torch.Tensor | None = None) -> None:
+                    fmt_out, residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                    step: int = 0, stream_id: int = 0, elem_base: int = 0) -> None:
     """sgd_apply_sum_q's step on the owned shard with theta left as it is: the momentum is updated
     (the same bits), and the update theta' - theta is block-quantized in fmt_out into `packed_out`
     (uint8, q_region_bytes(theta.numel(), fmt_out): one region). residual (fp32, theta's size): the
     owner's error feedback, added before and rewritten after the quantization
-    (edt_sgd_delta_sum_q: the quantized gather's phase 2')."""
+    (edt_sgd_delta_sum_q: the quantized gather's phase 2'). rounding='stochastic'
+    (edt_sgd_delta_sum_q_sr, no residual): delta_partial_q's keywords, elem_base being the shard's
+    start in the arena."""
     lib = L.lib()
+    sr = _stochastic(rounding, residual, seed, step, stream_id, elem_base)
     L.require_device(theta, momentum, packed_out, residual, *regions)
     n = theta.numel()
     code_in, code_out = _qfmt(fmt_in), _qfmt(fmt_out)
@@ -278,6 +310,13 @@ def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, mo
         raise L.EdtError("packed_out: a uint8 buffer of q_region_bytes(theta's size, fmt_out)")
     if residual is not None and (residual.dtype != torch.float32 or residual.numel() != n):
         raise L.EdtError("residual must be a float32 buffer of theta's size")
+    if sr:
+        L.check(lib.edt_sgd_delta_sum_q_sr(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions),
+                                           code_in, L.ptr(momentum), int(has_momentum), n, float(lr),
+                                           float(momentum_coef), int(nesterov), L.ptr(packed_out), code_out, int(seed),
+                                           int(step), int(stream_id), int(elem_base), L.stream_ptr(theta.device)),
+                "edt_sgd_delta_sum_q_sr")
+        return
     L.check(lib.edt_sgd_delta_sum_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code_in,
                                     L.ptr(momentum), int(has_momentum), n, float(lr), float(momentum_coef),
                                     int(nesterov), L.ptr(residual), L.ptr(packed_out), code_out,

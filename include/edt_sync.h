@@ -172,6 +172,29 @@ int edt_sgd_apply_sum(void* theta_g, int gdt, const float* const* acc_f32, int n
  * fp32 subnormal inputs are outside the bit-exact contract (finite output within one grid step). */
 typedef enum { EDT_MXFP8 = 0, EDT_MXFP4 = 1 } edt_qfmt_t;
 
+/* How the encoder picks an element's grid neighbour. EDT_ROUND_NEAREST is the rule above (every entry
+ * without _sr). EDT_ROUND_STOCHASTIC (the *_sr entries below; opt-in) keeps blocks,
+ * packing, region layout, the non-finite rule and the decoder, and changes the encoder only:
+ *   scale      e = floor(log2(amax)) - emax as above; if amax * 2^-e exceeds the element maximum (448 /
+ *              6), e + 1 instead, so no finite element of the block saturates; byte = clamp(e + 127, 0,
+ *              254) (at the 254 clamp elements may still saturate: outside the unbiased contract); an
+ *              all-zero block stores byte 0
+ *   elements   a = |v| * 2^-e (exact), k = max(floor(log2 a), EMIN) (EMIN = -6 / 0), q = 2^(k - MB)
+ *              (MB = 3 / 1), t = a / q (exact), lo = floor(t), f16 = floor((t - lo) * 2^16); the
+ *              element is (lo + up) * q with up = (r16 < f16), r16 the element's 16 random bits. The
+ *              sign is kept, for values that round to zero too. A value on the grid never moves
+ *              (f16 = 0); P(up) is within 2^-16 of the exact fraction.
+ *   r16        Philox4x32 with EDT_PHILOX_ROUNDS rounds (M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 =
+ *              0x9E3779B9, W1 = 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter =
+ *              (g & 0xffffffff, g >> 32, step & 0xffffffff, stream_id), g = global element index / 8.
+ *              The four output words serve elements 8g .. 8g+7: element 8g + j takes bits
+ *              16*(j%2) .. 16*(j%2)+15 of word j/2. The bits depend on seed, step, stream_id and the
+ *              global element index only — not on the grid, the bucket boundaries or the dtypes.
+ * Stochastic rounding takes no residual: it is unbiased in expectation and carries no state beyond
+ * the seed and the step counter. */
+typedef enum { EDT_ROUND_NEAREST = 0, EDT_ROUND_STOCHASTIC = 1 } edt_round_t;
+#define EDT_PHILOX_ROUNDS 10
+
 /* Bytes of one region of region_elems elements (HOST function; 0 for an unknown fmt or a
  * region_elems that is not a multiple of 512). */
 uint64_t edt_q_region_bytes(uint64_t region_elems, int fmt);
@@ -185,6 +208,15 @@ uint64_t edt_q_region_bytes(uint64_t region_elems, int fmt);
 int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
                         int K_total, uint64_t n, uint64_t region_elems, int fmt, float* residual, void* packed,
                         void* stream);
+
+/* edt_delta_partial_q with EDT_ROUND_STOCHASTIC (no residual). elem_base (a multiple of 8) is the
+ * global index of the call's first element: element i of the call draws the bits of global element
+ * elem_base + i, so a bucketed schedule (one call per bucket, elem_base = the bucket's start) writes
+ * the same bytes as one call over the whole arena. EDT_ERR_ARG as edt_delta_partial_q, and when
+ * elem_base % 8 != 0. */
+int edt_delta_partial_q_sr(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                           int K_total, uint64_t n, uint64_t region_elems, int fmt, void* packed, uint64_t seed,
+                           uint64_t step, uint32_t stream_id, uint64_t elem_base, void* stream);
 
 /* Phase 2: edt_sgd_apply_sum on nacc quantized regions of n elements each (regions[0..nacc),
  * device pointers): grad = -round_g(((D(q_0) + D(q_1)) + ...) + D(q_{nacc-1})) in fp32, that
@@ -211,6 +243,14 @@ int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int 
 int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in, void* momentum,
                         int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, float* residual,
                         void* packed_out, int fmt_out, void* stream);
+
+/* edt_sgd_delta_sum_q with the update quantized under EDT_ROUND_STOCHASTIC (no residual): the sum,
+ * the SGD update and the momentum bits are edt_sgd_delta_sum_q's; element i of the shard draws the
+ * bits of global element elem_base + i (elem_base % 8 == 0: the shard's start in the arena). */
+int edt_sgd_delta_sum_q_sr(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
+                           void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                           void* packed_out, int fmt_out, uint64_t seed, uint64_t step, uint32_t stream_id,
+                           uint64_t elem_base, void* stream);
 
 /* Phase 3 over a bucket of n elements: theta = round_g(f32(theta) + D(q)), one fp32 add then RNE to
  * theta's dtype. `packed` holds n / region_elems regions back to back, each of region_elems

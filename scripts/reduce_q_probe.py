@@ -20,6 +20,15 @@ the same operands (plain, gather, plain, gather, plain), each kernel timed — p
 all-gather fills every slot with this rank's own region, so phase 3 reads real blocks.
 
     python scripts/reduce_q_probe.py --gather-format mxfp8
+
+--rounding stochastic probes stochastic rounding instead (reduce_q with rounding="stochastic"): per
+group — world 1 / 8 x bf16 / fp32 workers x mxfp8 / mxfp4 partials, with --gather-format also the
+quantized gather in that format — error feedback off (the floor), error feedback on (what
+stochastic rounding replaces) and stochastic rounding alternate in this process on the same operands
+(off, on, sr, off, on, sr), each kernel timed by HIP events; the ratios sr / off and sr / on are
+formed within the run. The result is merged into profiles/sr_probe.json under the gather format.
+
+    python scripts/reduce_q_probe.py --rounding stochastic [--gather-format mxfp8]
 """
 from __future__ import annotations
 
@@ -61,12 +70,13 @@ def loopback(world: int):
     return Loopback()
 
 
-def measure(layout, wdt, world, mode, fmt, ef, steps, warmup, dev, seed=0, gather=None):
+def measure(layout, wdt, world, mode, fmt, ef, steps, warmup, dev, seed=0, gather=None, rounding="nearest"):
     from evolutionarydistributedtraining_amd.distributed import ShardedOuterSync
     k_local = 8 // world
     s = ShardedOuterSync(layout, torch.float32, wdt, k_local, dev, mode=mode, broadcast="theta", comm=loopback(world),
                          **({"wire_format": fmt, "error_feedback": ef} if mode == "reduce_q" else {}),
-                         **({"gather_format": gather} if gather else {}))
+                         **({"gather_format": gather} if gather else {}),
+                         **({"rounding": rounding, "seed": 0x5eed} if rounding != "nearest" else {}))
     g = torch.Generator(device=dev).manual_seed(seed)
     s.theta_buf.normal_(0, 0.02, generator=g)
     for w in s.worker_bufs:
@@ -177,6 +187,55 @@ def gather_main(a, layout, dev):
         f.write("\n")
 
 
+def sr_main(a, layout, dev):
+    """Stochastic rounding against error feedback off and on, per group, interleaved in one process."""
+    from evolutionarydistributedtraining_amd import _lib as L
+    gf = a.gather_format
+    phases = ("phase1_ms", "phase2_ms") + (("phase3_ms",) if gf else ()) + ("ms",)
+    groups = []
+    for world in (1, 8):
+        for name, wdt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+            for fmt in ("mxfp8", "mxfp4"):
+                run = lambda ef, rnd="nearest": measure(layout, wdt, world, "reduce_q", fmt, ef, a.steps, a.warmup, dev,
+                                                        gather=gf, rounding=rnd)
+                rows = {"ef_off": [], "ef_on": [], "sr": []}
+                for _ in range(a.rounds):
+                    rows["ef_off"].append(run(False))
+                    rows["ef_on"].append(run(True))
+                    rows["sr"].append(run(False, "stochastic"))
+                grp = {"world": world, "workers": name, "theta": "f32", "k_local": 8 // world, "wire_format": fmt,
+                       "gather_format": gf}
+                for key, rs in rows.items():
+                    grp[key] = {ph: round(statistics.median(r[ph] for r in rs), 4) for ph in phases}
+                    grp[key]["repeats_ms"] = [r["ms"] for r in rs]
+                    grp[key]["repeats_phase1_ms"] = [r["phase1_ms"] for r in rs]
+                    grp[key]["kernel_bytes"] = rs[0]["kernel_bytes"]
+                for ph in phases:
+                    tag = "total" if ph == "ms" else ph[:-3]
+                    grp[f"sr_over_ef_off_{tag}"] = round(grp["sr"][ph] / grp["ef_off"][ph], 4)
+                    grp[f"sr_over_ef_on_{tag}"] = round(grp["sr"][ph] / grp["ef_on"][ph], 4)
+                grp["sr_not_slower_than_ef_on"] = grp["sr"]["ms"] <= grp["ef_on"]["ms"]
+                groups.append(grp)
+                print(json.dumps(grp), flush=True)
+    out = a.out or os.path.join(ROOT, "profiles", "sr_probe.json")
+    try:
+        with open(out) as f:
+            res = json.load(f)
+        assert res.get("probe") == "sr_probe"
+    except (OSError, ValueError, AssertionError):
+        res = {"probe": "sr_probe", "runs": {}}
+    res.update({"layout": a.layout, "elements": layout.total, "K": 8, "device": torch.cuda.get_device_name(0),
+                "note": "local kernels only, one GPU, loopback communicator, HIP-event times per kernel: medians over "
+                        "`steps` steps, then over `rounds` alternating runs; ef_off is the floor, ef_on what stochastic "
+                        "rounding replaces; nothing is measured of the links"})
+    res["runs"]["gather_" + (gf or "none")] = {"steps": a.steps, "warmup": a.warmup, "rounds": a.rounds,
+                                               "library_sha256": L.library_sha256(), "groups": groups}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -186,11 +245,16 @@ def main():
                                                 "with --gather-format)")
     ap.add_argument("--gather-format", choices=("mxfp8", "mxfp4"), default=None,
                     help="probe the quantized gather next to plain reduce_q instead")
+    ap.add_argument("--rounding", choices=("nearest", "stochastic"), default="nearest",
+                    help="stochastic: probe stochastic rounding against error feedback off / on (profiles/sr_probe.json)")
+    ap.add_argument("--rounds", type=int, default=3, help="--rounding stochastic: alternating runs per setting")
     a = ap.parse_args()
     from evolutionarydistributedtraining_amd import _lib as L
     from evolutionarydistributedtraining_amd.layouts import LAYOUTS
     dev = torch.device("cuda:0")
     layout = LAYOUTS[a.layout]()
+    if a.rounding == "stochastic":
+        return sr_main(a, layout, dev)
     if a.gather_format:
         return gather_main(a, layout, dev)
     a.out = a.out or os.path.join(ROOT, "profiles", "reduce_q_probe.json")
