@@ -21,7 +21,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in ("edt_outer.hip", "edt_merge.hip", "edt_slerp.hip", "edt_abi.hip",
                                            "edt_quant.hip")]
 HEADER = os.path.join(ROOT, "include", "edt_sync.h")
-DEPS = SOURCES + [HEADER, os.path.join(CSRC, "edt_common.h")]
+DEPS = SOURCES + [HEADER, os.path.join(CSRC, "edt_common.h"), os.path.join(CSRC, "edt_step.h")]
 OUT = os.path.join(PKG_DIR, "libedt_sync.so")
 
 ARCH = "gfx950"

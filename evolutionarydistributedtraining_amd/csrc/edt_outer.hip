@@ -1,7 +1,7 @@
 // edt_outer.hip — the DiLoCo outer step (EDT_LM/diloco.py:238-289): the fused kernel over flat
 // arenas or tensor lists, its sharded halves (partial sums, SGD on a shard) and the stream-ceiling
 // probe, with their C ABI entries (include/edt_sync.h).
-#include "edt_common.h"
+#include "edt_step.h"
 
 namespace {
 
@@ -73,24 +73,7 @@ __device__ __forceinline__ void outer_elems(const A& a, uint64_t i) {
         for (int j = 0; j < N; ++j) acc[j] = 0.f;
     }
     const int K = KC > 0 ? KC : a.K;
-    auto body = [&](int k) {
-        float w[N];
-        ld<WDT, N, nt_worker_loads<WDT, H2>(), H2>(a.wp(k), i, w);
-#pragma unroll
-        for (int j = 0; j < N; ++j) w[j] = w[j] - g[j];              // trained - base
-        rnd<GDT>(w);
-        if constexpr (DIV) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) w[j] = w[j] / a.kdiv;        // delta / num_models
-        } else {
-#pragma unroll
-            for (int j = 0; j < N; ++j) w[j] = w[j] * a.kinv;
-        }
-        rnd<GDT>(w);
-#pragma unroll
-        for (int j = 0; j < N; ++j) acc[j] = acc[j] + w[j];          // acc += delta / K
-        if constexpr (MODE != MODE_PARTIAL) rnd<GDT>(acc);
-    };
+    auto body = [&](int k) { add_delta<GDT, WDT, DIV, N, H2, MODE != MODE_PARTIAL>(a, k, g, acc, i); };
     if constexpr (KC > 0) {
 #pragma unroll
         for (int k = 0; k < KC; ++k) body(k);
@@ -236,37 +219,6 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_list_kernel(ListA
     for (uint64_t b = blockIdx.x; b < L.chunks; b += gridDim.x) outer_list_chunk<GDT, WDT, KC, DIV>(L, prefix, b);
 }
 
-// SGD from a reduced fp32 sum (sharded multi-GPU step).
-template <int GDT, int N>
-__global__ __launch_bounds__(kBlock) void sgd_apply_kernel(void* theta, const float* acc, void* mom,
-                                                           uint64_t n, SgdScalars s) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    auto elems = [&](auto tagN, uint64_t i) {
-        constexpr int M = decltype(tagN)::value;
-        float g[M], a[M], grad[M], b_in[M];
-        ld<GDT, M>(theta, i, g);
-        ld<EDT_F32, M>(acc, i, a);
-        ld_momentum<GDT, M>(mom, i, s, b_in);
-        rnd<GDT>(a);
-#pragma unroll
-        for (int j = 0; j < M; ++j) grad[j] = -a[j];
-        sgd_update<GDT, M>(g, grad, mom, i, s, b_in);
-        st<GDT, M>(theta, i, g);
-    };
-    using V8 = std::integral_constant<int, kVec>;
-    using V1 = std::integral_constant<int, 1>;
-    if constexpr (N == kVec) {
-        const uint64_t nv = n / kVec;
-        for (uint64_t v = tid; v < nv; v += stride) elems(V8{}, v * kVec);
-        const uint64_t t = nv * kVec + tid;
-        if (t < n) elems(V1{}, t);
-    } else {
-        for (uint64_t e = tid; e < n; e += stride) elems(V1{}, e);
-    }
-}
-
-
 // SGD from N per-rank fp32 partial sums of the same shard, summed in rank order (the sharded
 // step's "reduce_ordered" schedule: an all-to-all delivers every rank's partial of the owned
 // shard, so the cross-rank sum has one fixed order whatever the collective library does).
@@ -277,36 +229,24 @@ struct Partials {
 template <int GDT, int N>
 __global__ __launch_bounds__(kBlock) void sgd_apply_sum_kernel(void* theta, Partials P, int np, void* mom,
                                                                uint64_t n, SgdScalars s) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    auto elems = [&](auto tagN, uint64_t i) {
+    for_vec_tail<N>(n, [&](auto tagN, uint64_t i) {
         constexpr int M = decltype(tagN)::value;
-        float g[M], a[M], grad[M], b_in[M];
-        ld<GDT, M>(theta, i, g);
-        ld_momentum<GDT, M>(mom, i, s, b_in);
-        ld<EDT_F32, M>(P.p[0], i, a);
-        for (int r = 1; r < np; ++r) {              // rank order
-            float x[M];
-            ld<EDT_F32, M>(P.p[r], i, x);
-#pragma unroll
-            for (int j = 0; j < M; ++j) a[j] = a[j] + x[j];
-        }
-        rnd<GDT>(a);
-#pragma unroll
-        for (int j = 0; j < M; ++j) grad[j] = -a[j];
-        sgd_update<GDT, M>(g, grad, mom, i, s, b_in);
+        float g0[M], g[M];
+        sgd_from_sum<GDT, M>(theta, mom, i, s, np, [&](int r, float (&x)[M]) { ld<EDT_F32, M>(P.p[r], i, x); }, g0, g);
         st<GDT, M>(theta, i, g);
-    };
-    using V8 = std::integral_constant<int, kVec>;
-    using V1 = std::integral_constant<int, 1>;
-    if constexpr (N == kVec) {
-        const uint64_t nv = n / kVec;
-        for (uint64_t v = tid; v < nv; v += stride) elems(V8{}, v * kVec);
-        const uint64_t t = nv * kVec + tid;
-        if (t < n) elems(V1{}, t);
-    } else {
-        for (uint64_t e = tid; e < n; e += stride) elems(V1{}, e);
-    }
+    });
+}
+
+// SGD from a reduced fp32 sum (the "reduce" schedule): the same step from one partial.
+template <int GDT, int N>
+__global__ __launch_bounds__(kBlock) void sgd_apply_kernel(void* theta, const float* acc, void* mom,
+                                                           uint64_t n, SgdScalars s) {
+    for_vec_tail<N>(n, [&](auto tagN, uint64_t i) {
+        constexpr int M = decltype(tagN)::value;
+        float g0[M], g[M];
+        sgd_from_sum<GDT, M>(theta, mom, i, s, 1, [&](int, float (&x)[M]) { ld<EDT_F32, M>(acc, i, x); }, g0, g);
+        st<GDT, M>(theta, i, g);
+    });
 }
 
 
@@ -357,58 +297,36 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void probe_kernel(OuterArgs 
 // ---------------------------------------------------------------------------------------
 // launch helpers
 
-template <int GDT, int WDT, int MODE, bool BC = false>
-int launch_outer_k(const OuterArgs& a, bool vec, hipStream_t s) {
-    const unsigned g = grid_for(a.n, vec);
-#define EDT_LAUNCH_K(KC, DIV)                                                                    \
-    do {                                                                                         \
-        if (vec) outer_kernel<GDT, WDT, KC, DIV, MODE, kVec, BC><<<g, kBlock, 0, s>>>(a);        \
-        else outer_kernel<GDT, WDT, KC, DIV, MODE, 1, BC><<<g, kBlock, 0, s>>>(a);               \
-    } while (0)
-    // compile-time worker counts for the common populations; the divisor is K_total
-    if constexpr (MODE == MODE_CHAIN) {
-        if (a.div_exact) EDT_LAUNCH_K(0, 1);
-        else EDT_LAUNCH_K(0, 0);
-        return check_launch("outer_kernel");
-    }
-    if (a.K == 1 && !a.div_exact) EDT_LAUNCH_K(1, 0);
-    else if (a.K == 2 && !a.div_exact) EDT_LAUNCH_K(2, 0);
-    else if (a.K == 3 && a.div_exact) EDT_LAUNCH_K(3, 1);
-    else if (a.K == 4 && !a.div_exact) EDT_LAUNCH_K(4, 0);
-    else if (a.K == 8 && !a.div_exact) EDT_LAUNCH_K(8, 0);
-    else if (a.div_exact) EDT_LAUNCH_K(0, 1);
-    else EDT_LAUNCH_K(0, 0);
-#undef EDT_LAUNCH_K
-    return check_launch("outer_kernel");
-}
-
 template <int MODE, bool BC = false>
 int launch_outer(int gdt, int wdt, const OuterArgs& a, bool vec, hipStream_t s) {
-    if (gdt == EDT_F32 && wdt == EDT_F32) return launch_outer_k<EDT_F32, EDT_F32, MODE, BC>(a, vec, s);
-    if (gdt == EDT_F32 && wdt == EDT_BF16) return launch_outer_k<EDT_F32, EDT_BF16, MODE, BC>(a, vec, s);
-    return launch_outer_k<EDT_BF16, EDT_BF16, MODE, BC>(a, vec, s);
+    const unsigned g = grid_for(a.n, vec);
+    const int kc = MODE == MODE_CHAIN ? 0 : a.K;        // chained launches always take the generic loop
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_kc_div<KC_FUSED>(kc, a.div_exact, [&](auto KC, auto DIV) {
+            return with_bool(vec, [&](auto V) {
+                constexpr int N = decltype(V)::value ? kVec : 1;
+                outer_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value, decltype(DIV)::value, MODE, N, BC>
+                    <<<g, kBlock, 0, s>>>(a);
+                return check_launch("outer_kernel");
+            });
+        });
+    });
 }
 
 constexpr uint64_t kListLdsMaxTensors = 8191;          // (T + 1) x 8 B <= 64 KiB of LDS
 
-template <int GDT, int WDT>
-int launch_list_k(const ListArgs& L, int div_exact, unsigned grid, hipStream_t s) {
+int launch_list(int gdt, int wdt, const ListArgs& L, bool div_exact, unsigned grid, hipStream_t s) {
     const bool lds = L.T <= kListLdsMaxTensors;
     const size_t shm = lds ? (size_t)(L.T + 1) * sizeof(uint64_t) : 0;
-#define EDT_LAUNCH_L(KC, DIV)                                                                    \
-    do {                                                                                         \
-        if (lds) outer_list_kernel<GDT, WDT, KC, DIV, true><<<grid, kBlock, shm, s>>>(L);        \
-        else outer_list_kernel<GDT, WDT, KC, DIV, false><<<grid, kBlock, 0, s>>>(L);             \
-    } while (0)
-    if (L.K == 1 && !div_exact) EDT_LAUNCH_L(1, 0);
-    else if (L.K == 2 && !div_exact) EDT_LAUNCH_L(2, 0);
-    else if (L.K == 3 && div_exact) EDT_LAUNCH_L(3, 1);
-    else if (L.K == 4 && !div_exact) EDT_LAUNCH_L(4, 0);
-    else if (L.K == 8 && !div_exact) EDT_LAUNCH_L(8, 0);
-    else if (div_exact) EDT_LAUNCH_L(0, 1);
-    else EDT_LAUNCH_L(0, 0);
-#undef EDT_LAUNCH_L
-    return check_launch("outer_list_kernel");
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_kc_div<KC_FUSED>(L.K, div_exact, [&](auto KC, auto DIV) {
+            return with_bool(lds, [&](auto LDS) {
+                outer_list_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value, decltype(DIV)::value,
+                                  decltype(LDS)::value><<<grid, kBlock, shm, s>>>(L);
+                return check_launch("outer_list_kernel");
+            });
+        });
+    });
 }
 
 
@@ -432,6 +350,26 @@ int fill_outer(OuterArgs& a, const void* theta, const void* const* theta_k, int 
     return EDT_OK;
 }
 
+// theta, the momentum (when the step uses one) and the K workers are 16-byte aligned: with every
+// further operand of the entry aligned too, the launch takes the 8-element kernels
+bool outer_vec(const void* theta, const void* momentum, const SgdScalars& sg, const void* const* theta_k, int K) {
+    bool vec = aligned16(theta) && (!sg.use_momentum || aligned16(momentum));
+    for (int k = 0; k < K; ++k) vec = vec && aligned16(theta_k[k]);
+    return vec;
+}
+
+// What the fused-step entries share after their dtype check: the argument block, the SGD scalars,
+// the momentum's null check and `vec` (outer_vec).
+int outer_prologue(OuterArgs& a, bool& vec, void* theta_g, int gdt, const void* const* theta_k, int K, void* momentum,
+                   int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov) {
+    int rc = fill_outer(a, theta_g, theta_k, K, K, n);
+    if (rc) return rc;
+    a.sgd = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
+    if (a.sgd.use_momentum && !momentum && n) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    a.mom = momentum;
+    vec = outer_vec(theta_g, momentum, a.sgd, theta_k, K);
+    return EDT_OK;
+}
 
 }  // namespace
 
@@ -452,17 +390,12 @@ int edt_probe_stream(void* theta_g, int gdt, const void* const* theta_k, int wdt
     if (n == 0) return EDT_OK;
     const unsigned g = grid_for(n, true);
     hipStream_t s = (hipStream_t)stream;
-    if (gdt == EDT_F32 && wdt == EDT_BF16) {
-        if (K == 8) probe_kernel<EDT_F32, EDT_BF16, 8><<<g, kBlock, 0, s>>>(a);
-        else probe_kernel<EDT_F32, EDT_BF16, 0><<<g, kBlock, 0, s>>>(a);
-    } else if (gdt == EDT_F32) {
-        if (K == 8) probe_kernel<EDT_F32, EDT_F32, 8><<<g, kBlock, 0, s>>>(a);
-        else probe_kernel<EDT_F32, EDT_F32, 0><<<g, kBlock, 0, s>>>(a);
-    } else {
-        if (K == 8) probe_kernel<EDT_BF16, EDT_BF16, 8><<<g, kBlock, 0, s>>>(a);
-        else probe_kernel<EDT_BF16, EDT_BF16, 0><<<g, kBlock, 0, s>>>(a);
-    }
-    return check_launch("probe_kernel");
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_bool(K == 8, [&](auto K8) {
+            probe_kernel<decltype(G)::value, decltype(W)::value, decltype(K8)::value ? 8 : 0><<<g, kBlock, 0, s>>>(a);
+            return check_launch("probe_kernel");
+        });
+    });
 }
 
 int edt_outer_step_bytes_per_elem(int gdt, int wdt, int K, int with_momentum) {
@@ -476,14 +409,10 @@ int edt_outer_step(void* theta_g, int gdt, const void* const* theta_k, int wdt, 
     g_err[0] = 0;
     if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
     OuterArgs a;
-    int rc = fill_outer(a, theta_g, theta_k, K, K, n);
+    bool vec;
+    int rc = outer_prologue(a, vec, theta_g, gdt, theta_k, K, momentum, has_momentum, n, lr, momentum_coef, nesterov);
     if (rc) return rc;
-    a.sgd = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
-    if (a.sgd.use_momentum && !momentum && n) return fail(EDT_ERR_ARG, "momentum buffer is null");
-    a.mom = momentum;
     if (n == 0) return EDT_OK;
-    bool vec = aligned16(theta_g) && (!a.sgd.use_momentum || aligned16(momentum));
-    for (int k = 0; k < K; ++k) vec = vec && aligned16(theta_k[k]);
     return launch_outer<MODE_FUSED>(gdt, wdt, a, vec, (hipStream_t)stream);
 }
 
@@ -493,15 +422,11 @@ int edt_outer_step_tail(void* theta_g, int gdt, const void* const* theta_k, int 
     g_err[0] = 0;
     if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
     OuterArgs a;
-    int rc = fill_outer(a, theta_g, theta_k, K, K, n);
+    bool vec;
+    int rc = outer_prologue(a, vec, theta_g, gdt, theta_k, K, momentum, has_momentum, n, lr, momentum_coef, nesterov);
     if (rc) return rc;
-    a.sgd = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
-    if (a.sgd.use_momentum && !momentum && n) return fail(EDT_ERR_ARG, "momentum buffer is null");
-    a.mom = momentum;
     if (gdt == EDT_BF16) a.sgd.tail = tail_bits;    // fp32: torch's tails are FMAs too, nothing to emulate
     if (n == 0) return EDT_OK;
-    bool vec = aligned16(theta_g) && (!a.sgd.use_momentum || aligned16(momentum));
-    for (int k = 0; k < K; ++k) vec = vec && aligned16(theta_k[k]);
     return launch_outer<MODE_FUSED>(gdt, wdt, a, vec, (hipStream_t)stream);
 }
 
@@ -516,11 +441,9 @@ int edt_outer_step_bcast(void* theta_g, int gdt, const void* const* theta_k, int
         return edt_outer_step(theta_g, gdt, theta_k, wdt, K, momentum, has_momentum, n, lr, momentum_coef, nesterov,
                               stream);
     OuterArgs a;
-    int rc = fill_outer(a, theta_g, theta_k, K, K, n);
+    bool vec;
+    int rc = outer_prologue(a, vec, theta_g, gdt, theta_k, K, momentum, has_momentum, n, lr, momentum_coef, nesterov);
     if (rc) return rc;
-    a.sgd = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
-    if (a.sgd.use_momentum && !momentum && n) return fail(EDT_ERR_ARG, "momentum buffer is null");
-    a.mom = momentum;
     if (!bcast) return fail(EDT_ERR_ARG, "bcast is null");
     const uintptr_t t0 = reinterpret_cast<uintptr_t>(theta_g), t1 = t0 + n * (gdt == EDT_BF16 ? 2 : 4);
     for (int k = 0; k < nbcast; ++k) {
@@ -531,8 +454,6 @@ int edt_outer_step_bcast(void* theta_g, int gdt, const void* const* theta_k, int
     }
     a.nbc = nbcast;
     if (n == 0) return EDT_OK;
-    bool vec = aligned16(theta_g) && (!a.sgd.use_momentum || aligned16(momentum));
-    for (int k = 0; k < K; ++k) vec = vec && aligned16(theta_k[k]);
     for (int k = 0; k < nbcast; ++k) vec = vec && aligned16(bcast[k]);
     return launch_outer<MODE_FUSED, true>(gdt, wdt, a, vec, (hipStream_t)stream);
 }
@@ -551,8 +472,8 @@ int edt_outer_step_ws(void* theta_g, int gdt, const void* const* theta_k, int wd
     const SgdScalars sg = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
     if (sg.use_momentum && !momentum && n) return fail(EDT_ERR_ARG, "momentum buffer is null");
     if (n == 0) return EDT_OK;
-    bool vec = aligned16(theta_g) && aligned16(workspace) && (!sg.use_momentum || aligned16(momentum));
-    for (int k = 0; k < K; ++k) vec = vec && theta_k[k] && aligned16(theta_k[k]);
+    bool vec = outer_vec(theta_g, momentum, sg, theta_k, K) && aligned16(workspace);
+    for (int k = 0; k < K; ++k) vec = vec && theta_k[k];    // a null worker (refused by its chunk's fill_outer)
     for (int k0 = 0; k0 < K; k0 += EDT_MAX_WORKERS) {       // worker order preserved across launches
         const int kc = K - k0 < EDT_MAX_WORKERS ? K - k0 : EDT_MAX_WORKERS;
         OuterArgs a;
@@ -650,11 +571,8 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     L.sgd = sg;
     L.tail = tail;
     L.tail_off = d + 4 * (uint64_t)T + 1 + (uint64_t)K * T;
-    const int div_exact = is_pow2(K) ? 0 : 1;
     const unsigned grid = chunks > kMaxBlocks ? (unsigned)kMaxBlocks : (unsigned)chunks;   // grid-stride
-    if (gdt == EDT_F32 && wdt == EDT_F32) return launch_list_k<EDT_F32, EDT_F32>(L, div_exact, grid, st);
-    if (gdt == EDT_F32) return launch_list_k<EDT_F32, EDT_BF16>(L, div_exact, grid, st);
-    return launch_list_k<EDT_BF16, EDT_BF16>(L, div_exact, grid, st);
+    return launch_list(gdt, wdt, L, !is_pow2(K), grid, st);
 }
 
 extern "C" {
@@ -696,52 +614,47 @@ int edt_delta_partial(const void* theta_g, int gdt, const void* const* theta_k, 
 int edt_sgd_apply_sum(void* theta_g, int gdt, const float* const* acc_f32, int nacc, void* momentum,
                       int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
     g_err[0] = 0;
-    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
-    if (nacc < 1 || nacc > EDT_MAX_WORKERS) return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc,
-                                                         EDT_MAX_WORKERS);
+    int rc = check_master_dtype(gdt);
+    if (!rc) rc = check_partial_count(nacc);
+    if (rc) return rc;
     if (n == 0) return EDT_OK;
     if (!theta_g || !acc_f32) return fail(EDT_ERR_ARG, "null buffer");
-    SgdScalars s = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
-    if (s.use_momentum && !momentum) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    SgdScalars s;
+    if ((rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum))) return rc;
     Partials P;
     memset(&P, 0, sizeof(P));
     bool vec = aligned16(theta_g) && (!s.use_momentum || aligned16(momentum));
-    for (int r = 0; r < nacc; ++r) {
-        if (!acc_f32[r]) return fail(EDT_ERR_ARG, "acc_f32[%d] is null", r);
-        P.p[r] = acc_f32[r];
-        vec = vec && aligned16(acc_f32[r]);
-    }
+    if ((rc = fill_table(P.p, acc_f32, nacc, "acc_f32", vec))) return rc;
     const unsigned g = grid_for(n, vec);
     hipStream_t st = (hipStream_t)stream;
-    if (gdt == EDT_F32) {
-        if (vec) sgd_apply_sum_kernel<EDT_F32, kVec><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-        else sgd_apply_sum_kernel<EDT_F32, 1><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-    } else {
-        if (vec) sgd_apply_sum_kernel<EDT_BF16, kVec><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-        else sgd_apply_sum_kernel<EDT_BF16, 1><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-    }
-    return check_launch("sgd_apply_sum_kernel");
+    return with_dtype(gdt, [&](auto G) {
+        return with_bool(vec, [&](auto V) {
+            sgd_apply_sum_kernel<decltype(G)::value, decltype(V)::value ? kVec : 1>
+                <<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+            return check_launch("sgd_apply_sum_kernel");
+        });
+    });
 }
 
 int edt_sgd_apply(void* theta_g, int gdt, const float* acc_f32, void* momentum, int has_momentum,
                   uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
     g_err[0] = 0;
-    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
+    int rc = check_master_dtype(gdt);
+    if (rc) return rc;
     if (n == 0) return EDT_OK;
     if (!theta_g || !acc_f32) return fail(EDT_ERR_ARG, "null buffer");
-    SgdScalars s = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
-    if (s.use_momentum && !momentum) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    SgdScalars s;
+    if ((rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum))) return rc;
     const bool vec = aligned16(theta_g) && aligned16(acc_f32) && (!s.use_momentum || aligned16(momentum));
     const unsigned g = grid_for(n, vec);
     hipStream_t st = (hipStream_t)stream;
-    if (gdt == EDT_F32) {
-        if (vec) sgd_apply_kernel<EDT_F32, kVec><<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s);
-        else sgd_apply_kernel<EDT_F32, 1><<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s);
-    } else {
-        if (vec) sgd_apply_kernel<EDT_BF16, kVec><<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s);
-        else sgd_apply_kernel<EDT_BF16, 1><<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s);
-    }
-    return check_launch("sgd_apply_kernel");
+    return with_dtype(gdt, [&](auto G) {
+        return with_bool(vec, [&](auto V) {
+            sgd_apply_kernel<decltype(G)::value, decltype(V)::value ? kVec : 1>
+                <<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s);
+            return check_launch("sgd_apply_kernel");
+        });
+    });
 }
 
 

@@ -1,9 +1,9 @@
 // edt_quant.hip — the block-quantized partial exchange of the sharded outer step (the "reduce_q"
 // schedule of distributed.ShardedOuterSync): phase 1 forms each rank's fp32 pseudo-gradient partial
-// (edt_delta_partial's math, bit for bit) and writes it as OCP MX blocks — MXFP8 (E4M3 elements)
-// or MXFP4 (E2M1 elements), 32 elements per E8M0 scale byte — without the fp32 partial ever
-// reaching HBM; phase 2 dequantizes the owned shard's N regions, sums them in rank order
-// (edt_sgd_apply_sum's order) and runs the SGD step. With the quantized gather (gather_format) the
+// (edt_delta_partial's, by the same code: edt_step.h) and writes it as OCP MX blocks — MXFP8 (E4M3
+// elements) or MXFP4 (E2M1 elements), 32 elements per E8M0 scale byte — without the fp32 partial ever
+// reaching HBM; phase 2 dequantizes the owned shard's N regions, sums them in rank order and runs
+// the SGD step (edt_sgd_apply_sum's, by the same code). With the quantized gather (gather_format) the
 // owner runs phase 2' instead: the same step, but theta is left alone and the update theta' - theta
 // is written as one more region (sharded error feedback); phase 3 then adds the dequantized updates
 // of a whole bucket to theta on every rank. The reference ships checkpoints over a shared disk
@@ -41,7 +41,7 @@
 // covers 512 elements = 16 blocks, and sizes are multiples of 512 so every wave is whole. Payload
 // leaves as one 8-byte (MXFP8) or 4-byte (MXFP4) store per lane, contiguous across the wave; the
 // 16 scale bytes of a wave are gathered across lanes into four dwords stored by lanes 0/16/32/48.
-#include "edt_common.h"
+#include "edt_step.h"
 
 namespace {
 
@@ -61,6 +61,7 @@ struct QPartialArgs {
     float kdiv;
     float kinv;
     QWorkers w;
+    __device__ __forceinline__ const void* wp(int k) const { return w.p[k]; }
 };
 
 // element formats: mantissa bits, smallest normal exponent, exponent bias, largest magnitude, emax
@@ -218,7 +219,21 @@ __device__ __forceinline__ void quant_store(const float (&acc)[kVec], float* res
     if ((lane & 15u) == 0) *reinterpret_cast<uint32_t*>(base + payload_bytes + (off >> 5)) = sw;
 }
 
-// Phase 1 for the 8 elements at i (a multiple of 8; the wave's 64 lanes cover 512 consecutive ones).
+// Addresses: tile = 512 elements = one wave, and a region is a whole number of tiles. The region
+// that element i (of a buffer of regions back to back) lies in, and i's offset inside that region.
+struct RegionOf {
+    uint64_t reg, off;
+};
+__device__ __forceinline__ RegionOf region_of(uint64_t i, uint64_t tiles_per_region) {
+    const uint64_t tile = i >> 9;
+    uint64_t reg;
+    if ((tile | tiles_per_region) >> 32) reg = tile / tiles_per_region;
+    else reg = (uint32_t)tile / (uint32_t)tiles_per_region;
+    return {reg, i - reg * (tiles_per_region << 9)};
+}
+
+// Phase 1 for the 8 elements at i (a multiple of 8; the wave's 64 lanes cover 512 consecutive ones):
+// edt_delta_partial's partial (add_delta per worker, the rounded quotients summed in fp32), quantized.
 template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF, int RND = EDT_ROUND_NEAREST>
 __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t i, const QSr& sr = QSr{}) {
     constexpr int N = kVec;
@@ -227,24 +242,7 @@ __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t 
 #pragma unroll
     for (int j = 0; j < N; ++j) acc[j] = 0.f;
     const int K = KC > 0 ? KC : a.K;
-    // edt_delta_partial's body (edt_outer.hip, MODE_PARTIAL): the rounded quotients summed in fp32
-    auto body = [&](int k) {
-        float w[N];
-        ld<WDT, N, nt_worker_loads<WDT, 4>()>(a.w.p[k], i, w);
-#pragma unroll
-        for (int j = 0; j < N; ++j) w[j] = w[j] - g[j];
-        rnd<GDT>(w);
-        if constexpr (DIV) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) w[j] = w[j] / a.kdiv;
-        } else {
-#pragma unroll
-            for (int j = 0; j < N; ++j) w[j] = w[j] * a.kinv;
-        }
-        rnd<GDT>(w);
-#pragma unroll
-        for (int j = 0; j < N; ++j) acc[j] = acc[j] + w[j];
-    };
+    auto body = [&](int k) { add_delta<GDT, WDT, DIV, N, 4, false>(a, k, g, acc, i); };   // the fp32 partial
     if constexpr (KC > 0) {
 #pragma unroll
         for (int k = 0; k < KC; ++k) body(k);
@@ -258,31 +256,21 @@ __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t 
 #pragma unroll
         for (int j = 0; j < N; ++j) acc[j] = acc[j] + r[j];          // p' = p + r
     }
-    // addresses: tile = 512 elements = one wave; a region is a whole number of tiles
-    const uint64_t tile = i >> 9;
-    uint64_t reg;
-    if ((tile | a.tiles_per_region) >> 32) reg = tile / a.tiles_per_region;
-    else reg = (uint32_t)tile / (uint32_t)a.tiles_per_region;
-    const uint64_t off = i - reg * (a.tiles_per_region << 9);        // element offset inside the region
-    uint8_t* base = a.packed + reg * a.region_bytes;
-    quant_store<FMT, EF, RND>(acc, a.residual, i, base, off, a.payload_bytes, sr);
+    const RegionOf r = region_of(i, a.tiles_per_region);
+    quant_store<FMT, EF, RND>(acc, a.residual, i, a.packed + r.reg * a.region_bytes, r.off, a.payload_bytes, sr);
 }
 
 template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
 __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_kernel(QPartialArgs a) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t nv = a.n / kVec;                      // n % 512 == 0: a wave is in or out as a whole
-    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride)
-        partial_q_elems<GDT, WDT, KC, DIV, FMT, EF>(a, v * kVec);
+    for_whole_waves(a.n, [&](uint64_t i) { partial_q_elems<GDT, WDT, KC, DIV, FMT, EF>(a, i); });
 }
 
 // phase 1 with stochastic rounding: the same partial, no residual, the draw of each lane's group
 template <int GDT, int WDT, int KC, int DIV, int FMT>
 __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_sr_kernel(QPartialArgs a, QSr sr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t nv = a.n / kVec;
-    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride)
-        partial_q_elems<GDT, WDT, KC, DIV, FMT, false, EDT_ROUND_STOCHASTIC>(a, v * kVec, sr);
+    for_whole_waves(a.n, [&](uint64_t i) {
+        partial_q_elems<GDT, WDT, KC, DIV, FMT, false, EDT_ROUND_STOCHASTIC>(a, i, sr);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -316,57 +304,29 @@ __device__ __forceinline__ void ld_q(const uint8_t* region, uint64_t n, uint64_t
     }
 }
 
+// edt_sgd_apply_sum's step (sgd_from_sum) with every rank's partial dequantized from its region
 template <int GDT, int FMT>
 __global__ __launch_bounds__(kBlock) void sgd_apply_sum_q_kernel(void* theta, QRegions P, int np, void* mom,
                                                                  uint64_t n, SgdScalars s) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t nv = n / kVec;
-    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
-        const uint64_t i = v * kVec;
-        float g[kVec], a[kVec], grad[kVec], b_in[kVec];
-        ld<GDT, kVec>(theta, i, g);
-        ld_momentum<GDT, kVec>(mom, i, s, b_in);
-        ld_q<FMT>(P.p[0], n, i, a);
-        for (int r = 1; r < np; ++r) {                  // rank order, as sgd_apply_sum_kernel
-            float x[kVec];
-            ld_q<FMT>(P.p[r], n, i, x);
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) a[j] = a[j] + x[j];
-        }
-        rnd<GDT>(a);
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) grad[j] = -a[j];
-        sgd_update<GDT, kVec>(g, grad, mom, i, s, b_in);
+    for_whole_waves(n, [&](uint64_t i) {
+        float g0[kVec], g[kVec];
+        sgd_from_sum<GDT, kVec>(theta, mom, i, s, np, [&](int r, float (&x)[kVec]) { ld_q<FMT>(P.p[r], n, i, x); },
+                                g0, g);
         st<GDT, kVec>(theta, i, g);
-    }
+    });
 }
 
 // phase 2': sgd_apply_sum_q_kernel's step on the owned shard, but theta stays as it is: the update
-// u = theta' - theta (+ the owner's residual with EF) leaves as one region of FOUT blocks
-template <int GDT, int FIN, int FOUT, bool EF>
-__global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_kernel(const void* theta, QRegions P, int np, void* mom,
-                                                                 uint64_t n, SgdScalars s, float* residual,
-                                                                 uint8_t* packed_out) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t nv = n / kVec;                        // n % 512 == 0: a wave is in or out as a whole
+// u = theta' - theta (+ the owner's residual with EF) leaves as one region of FOUT blocks, rounded
+// to nearest (with or without EF) or stochastically (RND, no residual)
+template <int GDT, int FIN, int FOUT, bool EF, int RND>
+__device__ __forceinline__ void delta_sum_q_body(const void* theta, const QRegions& P, int np, void* mom, uint64_t n,
+                                                 const SgdScalars& s, float* residual, uint8_t* packed_out,
+                                                 const QSr& sr) {
     const uint64_t payload = n / 8 * QFmt<FOUT>::BITS;
-    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
-        const uint64_t i = v * kVec;
-        float g0[kVec], g[kVec], a[kVec], grad[kVec], b_in[kVec];
-        ld<GDT, kVec>(theta, i, g0);
-        ld_momentum<GDT, kVec>(mom, i, s, b_in);
-        ld_q<FIN>(P.p[0], n, i, a);
-        for (int r = 1; r < np; ++r) {                  // rank order, as sgd_apply_sum_q_kernel
-            float x[kVec];
-            ld_q<FIN>(P.p[r], n, i, x);
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) a[j] = a[j] + x[j];
-        }
-        rnd<GDT>(a);
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) { grad[j] = -a[j]; g[j] = g0[j]; }
-        sgd_update<GDT, kVec>(g, grad, mom, i, s, b_in);
-        float u[kVec];
+    for_whole_waves(n, [&](uint64_t i) {
+        float g0[kVec], g[kVec], u[kVec];
+        sgd_from_sum<GDT, kVec>(theta, mom, i, s, np, [&](int r, float (&x)[kVec]) { ld_q<FIN>(P.p[r], n, i, x); }, g0, g);
 #pragma unroll
         for (int j = 0; j < kVec; ++j) u[j] = g[j] - g0[j];               // u = theta' - theta
         if constexpr (EF) {
@@ -375,115 +335,85 @@ __global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_kernel(const void* the
 #pragma unroll
             for (int j = 0; j < kVec; ++j) u[j] = u[j] + r[j];            // u' = u + r_g
         }
-        quant_store<FOUT, EF>(u, residual, i, packed_out, i, payload);
-    }
+        quant_store<FOUT, EF, RND>(u, residual, i, packed_out, i, payload, sr);
+    });
 }
 
-// phase 2' with stochastic rounding of the update: sgd_delta_sum_q_kernel's step without a residual
-// (the nearest kernel above keeps its own text, so its code stays what it was)
+template <int GDT, int FIN, int FOUT, bool EF>
+__global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_kernel(const void* theta, QRegions P, int np, void* mom,
+                                                                 uint64_t n, SgdScalars s, float* residual,
+                                                                 uint8_t* packed_out) {
+    delta_sum_q_body<GDT, FIN, FOUT, EF, EDT_ROUND_NEAREST>(theta, P, np, mom, n, s, residual, packed_out, QSr{});
+}
+
 template <int GDT, int FIN, int FOUT>
 __global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_sr_kernel(const void* theta, QRegions P, int np, void* mom,
                                                                     uint64_t n, SgdScalars s, uint8_t* packed_out,
                                                                     QSr sr) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t nv = n / kVec;
-    const uint64_t payload = n / 8 * QFmt<FOUT>::BITS;
-    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
-        const uint64_t i = v * kVec;
-        float g0[kVec], g[kVec], a[kVec], grad[kVec], b_in[kVec];
-        ld<GDT, kVec>(theta, i, g0);
-        ld_momentum<GDT, kVec>(mom, i, s, b_in);
-        ld_q<FIN>(P.p[0], n, i, a);
-        for (int r = 1; r < np; ++r) {
-            float x[kVec];
-            ld_q<FIN>(P.p[r], n, i, x);
-#pragma unroll
-            for (int j = 0; j < kVec; ++j) a[j] = a[j] + x[j];
-        }
-        rnd<GDT>(a);
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) { grad[j] = -a[j]; g[j] = g0[j]; }
-        sgd_update<GDT, kVec>(g, grad, mom, i, s, b_in);
-        float u[kVec];
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) u[j] = g[j] - g0[j];
-        quant_store<FOUT, false, EDT_ROUND_STOCHASTIC>(u, nullptr, i, packed_out, i, payload, sr);
-    }
+    delta_sum_q_body<GDT, FIN, FOUT, false, EDT_ROUND_STOCHASTIC>(theta, P, np, mom, n, s, nullptr, packed_out, sr);
 }
 
 // phase 3: theta <- round_g(theta + D(q)) over a bucket of n / region_elems regions back to back
 template <int GDT, int FMT>
 __global__ __launch_bounds__(kBlock) void apply_delta_q_kernel(void* theta, const uint8_t* packed, uint64_t n,
                                                                uint64_t tiles_per_region, uint64_t region_bytes) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t nv = n / kVec;
-    const uint64_t region_elems = tiles_per_region << 9;
-    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) {
-        const uint64_t i = v * kVec;
-        const uint64_t tile = i >> 9;
-        uint64_t reg;
-        if ((tile | tiles_per_region) >> 32) reg = tile / tiles_per_region;
-        else reg = (uint32_t)tile / (uint32_t)tiles_per_region;
+    for_whole_waves(n, [&](uint64_t i) {
+        const RegionOf r = region_of(i, tiles_per_region);
         float g[kVec], d[kVec];
         ld<GDT, kVec>(theta, i, g);
-        ld_q<FMT>(packed + reg * region_bytes, region_elems, i - reg * region_elems, d);
+        ld_q<FMT>(packed + r.reg * region_bytes, tiles_per_region << 9, r.off, d);
 #pragma unroll
         for (int j = 0; j < kVec; ++j) g[j] = g[j] + d[j];
         rnd<GDT>(g);
         st<GDT, kVec>(theta, i, g);
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------
-// launch helpers
+// launch helpers (sr: the stochastic-rounding kernel; else nearest, with error feedback when there
+// is a residual)
 
 inline int fmt_bits(int fmt) { return fmt == EDT_MXFP8 ? 8 : fmt == EDT_MXFP4 ? 4 : 0; }
 
-template <int GDT, int WDT, int FMT, bool EF>
-int launch_partial_q_k(const QPartialArgs& a, bool div_exact, hipStream_t s) {
+int launch_partial_q(int gdt, int wdt, int fmt, const QPartialArgs& a, const QSr* sr, bool div_exact, hipStream_t s) {
     const unsigned g = grid_for(a.n, true);
-    if (a.K == 8 && !div_exact) delta_partial_q_kernel<GDT, WDT, 8, 0, FMT, EF><<<g, kBlock, 0, s>>>(a);
-    else if (div_exact) delta_partial_q_kernel<GDT, WDT, 0, 1, FMT, EF><<<g, kBlock, 0, s>>>(a);
-    else delta_partial_q_kernel<GDT, WDT, 0, 0, FMT, EF><<<g, kBlock, 0, s>>>(a);
-    return check_launch("delta_partial_q_kernel");
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_fmt(fmt, [&](auto F) {
+            return with_kc_div<KC_QUANT>(a.K, div_exact, [&](auto KC, auto DIV) {
+                constexpr int GDT = decltype(G)::value, WDT = decltype(W)::value, FMT = decltype(F)::value;
+                constexpr int KCV = decltype(KC)::value, DIVV = decltype(DIV)::value;
+                if (sr) {
+                    delta_partial_q_sr_kernel<GDT, WDT, KCV, DIVV, FMT><<<g, kBlock, 0, s>>>(a, *sr);
+                    return check_launch("delta_partial_q_sr_kernel");
+                }
+                return with_bool(a.residual != nullptr, [&](auto EF) {
+                    delta_partial_q_kernel<GDT, WDT, KCV, DIVV, FMT, decltype(EF)::value><<<g, kBlock, 0, s>>>(a);
+                    return check_launch("delta_partial_q_kernel");
+                });
+            });
+        });
+    });
 }
 
-template <int GDT, int WDT>
-int launch_partial_q(const QPartialArgs& a, int fmt, bool div_exact, hipStream_t s) {
-    if (fmt == EDT_MXFP8)
-        return a.residual ? launch_partial_q_k<GDT, WDT, EDT_MXFP8, true>(a, div_exact, s)
-                          : launch_partial_q_k<GDT, WDT, EDT_MXFP8, false>(a, div_exact, s);
-    return a.residual ? launch_partial_q_k<GDT, WDT, EDT_MXFP4, true>(a, div_exact, s)
-                      : launch_partial_q_k<GDT, WDT, EDT_MXFP4, false>(a, div_exact, s);
-}
-
-template <int GDT, int WDT, int FMT>
-int launch_partial_q_sr_k(const QPartialArgs& a, const QSr& sr, bool div_exact, hipStream_t s) {
-    const unsigned g = grid_for(a.n, true);
-    if (a.K == 8 && !div_exact) delta_partial_q_sr_kernel<GDT, WDT, 8, 0, FMT><<<g, kBlock, 0, s>>>(a, sr);
-    else if (div_exact) delta_partial_q_sr_kernel<GDT, WDT, 0, 1, FMT><<<g, kBlock, 0, s>>>(a, sr);
-    else delta_partial_q_sr_kernel<GDT, WDT, 0, 0, FMT><<<g, kBlock, 0, s>>>(a, sr);
-    return check_launch("delta_partial_q_sr_kernel");
-}
-
-template <int GDT, int WDT>
-int launch_partial_q_sr(const QPartialArgs& a, const QSr& sr, int fmt, bool div_exact, hipStream_t s) {
-    if (fmt == EDT_MXFP8) return launch_partial_q_sr_k<GDT, WDT, EDT_MXFP8>(a, sr, div_exact, s);
-    return launch_partial_q_sr_k<GDT, WDT, EDT_MXFP4>(a, sr, div_exact, s);
-}
-
-template <int GDT>
-void launch_delta_sum_q_sr(const void* theta, const QRegions& P, int np, int fmt_in, void* mom, uint64_t n,
-                           const SgdScalars& sc, uint8_t* out, int fmt_out, const QSr& sr, hipStream_t s) {
+int launch_delta_sum_q(int gdt, int fmt_in, int fmt_out, const void* theta, const QRegions& P, int np, void* mom,
+                       uint64_t n, const SgdScalars& sc, float* residual, uint8_t* out, const QSr* sr, hipStream_t s) {
     const unsigned g = grid_for(n, true);
-    if (fmt_in == EDT_MXFP8 && fmt_out == EDT_MXFP8)
-        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP8, EDT_MXFP8><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
-    else if (fmt_in == EDT_MXFP8)
-        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP8, EDT_MXFP4><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
-    else if (fmt_out == EDT_MXFP8)
-        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP4, EDT_MXFP8><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
-    else
-        sgd_delta_sum_q_sr_kernel<GDT, EDT_MXFP4, EDT_MXFP4><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, sr);
+    return with_dtype(gdt, [&](auto G) {
+        return with_fmt(fmt_in, [&](auto FI) {
+            return with_fmt(fmt_out, [&](auto FO) {
+                constexpr int GDT = decltype(G)::value, FIN = decltype(FI)::value, FOUT = decltype(FO)::value;
+                if (sr) {
+                    sgd_delta_sum_q_sr_kernel<GDT, FIN, FOUT><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, *sr);
+                    return check_launch("sgd_delta_sum_q_sr_kernel");
+                }
+                return with_bool(residual != nullptr, [&](auto EF) {
+                    sgd_delta_sum_q_kernel<GDT, FIN, FOUT, decltype(EF)::value>
+                        <<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out);
+                    return check_launch("sgd_delta_sum_q_kernel");
+                });
+            });
+        });
+    });
 }
 
 inline QSr make_sr(uint64_t seed, uint64_t step, uint32_t stream_id, uint64_t elem_base) {
@@ -496,25 +426,33 @@ inline QSr make_sr(uint64_t seed, uint64_t step, uint32_t stream_id, uint64_t el
     return sr;
 }
 
-template <int GDT, int FIN, int FOUT>
-void launch_delta_sum_q_e(const void* theta, const QRegions& P, int np, void* mom, uint64_t n, const SgdScalars& sc,
-                          float* residual, uint8_t* out, hipStream_t s) {
-    const unsigned g = grid_for(n, true);
-    if (residual) sgd_delta_sum_q_kernel<GDT, FIN, FOUT, true><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out);
-    else sgd_delta_sum_q_kernel<GDT, FIN, FOUT, false><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out);
+// ---------------------------------------------------------------------------------------
+// argument checks the entries share
+
+int check_fmt(int fmt) {
+    if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
+    return EDT_OK;
 }
 
-template <int GDT>
-void launch_delta_sum_q(const void* theta, const QRegions& P, int np, int fmt_in, void* mom, uint64_t n,
-                        const SgdScalars& sc, float* residual, uint8_t* out, int fmt_out, hipStream_t s) {
-    if (fmt_in == EDT_MXFP8 && fmt_out == EDT_MXFP8)
-        launch_delta_sum_q_e<GDT, EDT_MXFP8, EDT_MXFP8>(theta, P, np, mom, n, sc, residual, out, s);
-    else if (fmt_in == EDT_MXFP8)
-        launch_delta_sum_q_e<GDT, EDT_MXFP8, EDT_MXFP4>(theta, P, np, mom, n, sc, residual, out, s);
-    else if (fmt_out == EDT_MXFP8)
-        launch_delta_sum_q_e<GDT, EDT_MXFP4, EDT_MXFP8>(theta, P, np, mom, n, sc, residual, out, s);
-    else
-        launch_delta_sum_q_e<GDT, EDT_MXFP4, EDT_MXFP4>(theta, P, np, mom, n, sc, residual, out, s);
+int check_regions(uint64_t n, uint64_t region_elems) {
+    if (region_elems == 0 || region_elems % 512)
+        return fail(EDT_ERR_ARG, "region_elems %llu is not a positive multiple of 512", (unsigned long long)region_elems);
+    if (n % region_elems)
+        return fail(EDT_ERR_ARG, "n = %llu is not a whole number of regions of %llu elements", (unsigned long long)n,
+                    (unsigned long long)region_elems);
+    return EDT_OK;
+}
+
+int check_one_region(uint64_t n) {
+    if (n % 512) return fail(EDT_ERR_ARG, "n = %llu is not a multiple of 512 (one region)", (unsigned long long)n);
+    return EDT_OK;
+}
+
+int check_elem_base(uint64_t elem_base) {
+    if (elem_base % 8)
+        return fail(EDT_ERR_ARG, "elem_base %llu is not a multiple of 8 (one lane's group of elements)",
+                    (unsigned long long)elem_base);
+    return EDT_OK;
 }
 
 }  // namespace
@@ -533,18 +471,12 @@ static int delta_partial_q_impl(const void* theta_g, int gdt, const void* const*
                                 const QSr* sr, uint64_t elem_base, void* stream) {
     g_err[0] = 0;
     if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
-    if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
+    if (int rc = check_fmt(fmt)) return rc;
     if (K_local < 1 || K_local > EDT_MAX_WORKERS)
         return fail(EDT_ERR_ARG, "worker count %d out of range [1, %d]", K_local, EDT_MAX_WORKERS);
     if (K_total < 1) return fail(EDT_ERR_ARG, "total worker count %d < 1", K_total);
-    if (region_elems == 0 || region_elems % 512)
-        return fail(EDT_ERR_ARG, "region_elems %llu is not a positive multiple of 512", (unsigned long long)region_elems);
-    if (n % region_elems)
-        return fail(EDT_ERR_ARG, "n = %llu is not a whole number of regions of %llu elements", (unsigned long long)n,
-                    (unsigned long long)region_elems);
-    if (elem_base % 8)
-        return fail(EDT_ERR_ARG, "elem_base %llu is not a multiple of 8 (one lane's group of elements)",
-                    (unsigned long long)elem_base);
+    if (int rc = check_regions(n, region_elems)) return rc;
+    if (int rc = check_elem_base(elem_base)) return rc;
     if (!theta_k) return fail(EDT_ERR_ARG, "theta_k is null");
     if (n == 0) return EDT_OK;
     if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
@@ -552,11 +484,7 @@ static int delta_partial_q_impl(const void* theta_g, int gdt, const void* const*
     QPartialArgs a;
     memset(&a, 0, sizeof(a));
     bool al = aligned16(theta_g) && aligned16(packed) && aligned16(residual);
-    for (int k = 0; k < K_local; ++k) {
-        if (!theta_k[k]) return fail(EDT_ERR_ARG, "theta_k[%d] is null", k);
-        a.w.p[k] = theta_k[k];
-        al = al && aligned16(theta_k[k]);
-    }
+    if (int rc = fill_table(a.w.p, theta_k, K_local, "theta_k", al)) return rc;
     if (!al) return fail(EDT_ERR_ARG, "the quantized partial needs 16-byte aligned operands");
     a.theta = theta_g;
     a.residual = residual;
@@ -568,16 +496,7 @@ static int delta_partial_q_impl(const void* theta_g, int gdt, const void* const*
     a.K = K_local;
     a.kdiv = (float)K_total;
     a.kinv = 1.0f / (float)K_total;
-    const bool div_exact = !is_pow2(K_total);
-    hipStream_t s = (hipStream_t)stream;
-    if (sr) {
-        if (gdt == EDT_F32 && wdt == EDT_F32) return launch_partial_q_sr<EDT_F32, EDT_F32>(a, *sr, fmt, div_exact, s);
-        if (gdt == EDT_F32) return launch_partial_q_sr<EDT_F32, EDT_BF16>(a, *sr, fmt, div_exact, s);
-        return launch_partial_q_sr<EDT_BF16, EDT_BF16>(a, *sr, fmt, div_exact, s);
-    }
-    if (gdt == EDT_F32 && wdt == EDT_F32) return launch_partial_q<EDT_F32, EDT_F32>(a, fmt, div_exact, s);
-    if (gdt == EDT_F32) return launch_partial_q<EDT_F32, EDT_BF16>(a, fmt, div_exact, s);
-    return launch_partial_q<EDT_BF16, EDT_BF16>(a, fmt, div_exact, s);
+    return launch_partial_q(gdt, wdt, fmt, a, sr, !is_pow2(K_total), (hipStream_t)stream);
 }
 
 int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
@@ -598,34 +517,28 @@ int edt_delta_partial_q_sr(const void* theta_g, int gdt, const void* const* thet
 int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
                         int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
     g_err[0] = 0;
-    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
-    if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
-    if (nacc < 1 || nacc > EDT_MAX_WORKERS)
-        return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc, EDT_MAX_WORKERS);
-    if (n % 512) return fail(EDT_ERR_ARG, "n = %llu is not a multiple of 512 (one region)", (unsigned long long)n);
+    if (int rc = check_master_dtype(gdt)) return rc;
+    if (int rc = check_fmt(fmt)) return rc;
+    if (int rc = check_partial_count(nacc)) return rc;
+    if (int rc = check_one_region(n)) return rc;
     if (n == 0) return EDT_OK;
     if (!theta_g || !regions) return fail(EDT_ERR_ARG, "null buffer");
-    SgdScalars s = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
-    if (s.use_momentum && !momentum) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    SgdScalars s;
+    if (int rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum)) return rc;
     QRegions P;
     memset(&P, 0, sizeof(P));
     bool al = aligned16(theta_g) && (!s.use_momentum || aligned16(momentum));
-    for (int r = 0; r < nacc; ++r) {
-        if (!regions[r]) return fail(EDT_ERR_ARG, "regions[%d] is null", r);
-        P.p[r] = static_cast<const uint8_t*>(regions[r]);
-        al = al && aligned16(regions[r]);
-    }
+    if (int rc = fill_table(P.p, regions, nacc, "regions", al)) return rc;
     if (!al) return fail(EDT_ERR_ARG, "the quantized sum needs 16-byte aligned operands");
     const unsigned g = grid_for(n, true);
     hipStream_t st = (hipStream_t)stream;
-    if (gdt == EDT_F32) {
-        if (fmt == EDT_MXFP8) sgd_apply_sum_q_kernel<EDT_F32, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-        else sgd_apply_sum_q_kernel<EDT_F32, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-    } else {
-        if (fmt == EDT_MXFP8) sgd_apply_sum_q_kernel<EDT_BF16, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-        else sgd_apply_sum_q_kernel<EDT_BF16, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-    }
-    return check_launch("sgd_apply_sum_q_kernel");
+    return with_dtype(gdt, [&](auto G) {
+        return with_fmt(fmt, [&](auto F) {
+            sgd_apply_sum_q_kernel<decltype(G)::value, decltype(F)::value>
+                <<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+            return check_launch("sgd_apply_sum_q_kernel");
+        });
+    });
 }
 
 // edt_sgd_delta_sum_q (sr null) and edt_sgd_delta_sum_q_sr
@@ -634,39 +547,24 @@ static int sgd_delta_sum_q_impl(const void* theta_g, int gdt, const void* const*
                                 int nesterov, float* residual, void* packed_out, int fmt_out, const QSr* sr,
                                 uint64_t elem_base, void* stream) {
     g_err[0] = 0;
-    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
-    if (!fmt_bits(fmt_in)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt_in);
-    if (!fmt_bits(fmt_out)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt_out);
-    if (nacc < 1 || nacc > EDT_MAX_WORKERS)
-        return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc, EDT_MAX_WORKERS);
-    if (n % 512) return fail(EDT_ERR_ARG, "n = %llu is not a multiple of 512 (one region)", (unsigned long long)n);
-    if (elem_base % 8)
-        return fail(EDT_ERR_ARG, "elem_base %llu is not a multiple of 8 (one lane's group of elements)",
-                    (unsigned long long)elem_base);
+    if (int rc = check_master_dtype(gdt)) return rc;
+    if (int rc = check_fmt(fmt_in)) return rc;
+    if (int rc = check_fmt(fmt_out)) return rc;
+    if (int rc = check_partial_count(nacc)) return rc;
+    if (int rc = check_one_region(n)) return rc;
+    if (int rc = check_elem_base(elem_base)) return rc;
     if (n == 0) return EDT_OK;
     if (!theta_g || !regions) return fail(EDT_ERR_ARG, "null buffer");
     if (!packed_out) return fail(EDT_ERR_ARG, "packed_out is null");
-    SgdScalars s = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
-    if (s.use_momentum && !momentum) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    SgdScalars s;
+    if (int rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum)) return rc;
     QRegions P;
     memset(&P, 0, sizeof(P));
     bool al = aligned16(theta_g) && (!s.use_momentum || aligned16(momentum)) && aligned16(residual) && aligned16(packed_out);
-    for (int r = 0; r < nacc; ++r) {
-        if (!regions[r]) return fail(EDT_ERR_ARG, "regions[%d] is null", r);
-        P.p[r] = static_cast<const uint8_t*>(regions[r]);
-        al = al && aligned16(regions[r]);
-    }
+    if (int rc = fill_table(P.p, regions, nacc, "regions", al)) return rc;
     if (!al) return fail(EDT_ERR_ARG, "the quantized update needs 16-byte aligned operands");
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* out = static_cast<uint8_t*>(packed_out);
-    if (sr) {
-        if (gdt == EDT_F32) launch_delta_sum_q_sr<EDT_F32>(theta_g, P, nacc, fmt_in, momentum, n, s, out, fmt_out, *sr, st);
-        else launch_delta_sum_q_sr<EDT_BF16>(theta_g, P, nacc, fmt_in, momentum, n, s, out, fmt_out, *sr, st);
-        return check_launch("sgd_delta_sum_q_sr_kernel");
-    }
-    if (gdt == EDT_F32) launch_delta_sum_q<EDT_F32>(theta_g, P, nacc, fmt_in, momentum, n, s, residual, out, fmt_out, st);
-    else launch_delta_sum_q<EDT_BF16>(theta_g, P, nacc, fmt_in, momentum, n, s, residual, out, fmt_out, st);
-    return check_launch("sgd_delta_sum_q_kernel");
+    return launch_delta_sum_q(gdt, fmt_in, fmt_out, theta_g, P, nacc, momentum, n, s, residual,
+                              static_cast<uint8_t*>(packed_out), sr, (hipStream_t)stream);
 }
 
 int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in, void* momentum,
@@ -688,13 +586,9 @@ int edt_sgd_delta_sum_q_sr(const void* theta_g, int gdt, const void* const* regi
 int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
                       void* stream) {
     g_err[0] = 0;
-    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
-    if (!fmt_bits(fmt)) return fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
-    if (region_elems == 0 || region_elems % 512)
-        return fail(EDT_ERR_ARG, "region_elems %llu is not a positive multiple of 512", (unsigned long long)region_elems);
-    if (n % region_elems)
-        return fail(EDT_ERR_ARG, "n = %llu is not a whole number of regions of %llu elements", (unsigned long long)n,
-                    (unsigned long long)region_elems);
+    if (int rc = check_master_dtype(gdt)) return rc;
+    if (int rc = check_fmt(fmt)) return rc;
+    if (int rc = check_regions(n, region_elems)) return rc;
     if (n == 0) return EDT_OK;
     if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
     if (!packed) return fail(EDT_ERR_ARG, "packed is null");
@@ -704,14 +598,12 @@ int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, ui
     hipStream_t st = (hipStream_t)stream;
     const uint8_t* q = static_cast<const uint8_t*>(packed);
     const uint64_t tpr = region_elems / 512, rb = edt_q_region_bytes(region_elems, fmt);
-    if (gdt == EDT_F32) {
-        if (fmt == EDT_MXFP8) apply_delta_q_kernel<EDT_F32, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
-        else apply_delta_q_kernel<EDT_F32, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
-    } else {
-        if (fmt == EDT_MXFP8) apply_delta_q_kernel<EDT_BF16, EDT_MXFP8><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
-        else apply_delta_q_kernel<EDT_BF16, EDT_MXFP4><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
-    }
-    return check_launch("apply_delta_q_kernel");
+    return with_dtype(gdt, [&](auto G) {
+        return with_fmt(fmt, [&](auto F) {
+            apply_delta_q_kernel<decltype(G)::value, decltype(F)::value><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
+            return check_launch("apply_delta_q_kernel");
+        });
+    });
 }
 
 }  // extern "C"

@@ -1,0 +1,183 @@
+// edt_step.h — the one text of the outer step's pieces that the fused kernels (edt_outer.hip) and
+// the quantized sharded kernels (edt_quant.hip) both run: a worker's delta added to the sum, the
+// rank-ordered sum of partials and the SGD step from it, the two grid-stride drivers, and the host
+// side's runtime-code -> compile-time-tag dispatch. Their bit-for-bit agreement across the fp32
+// and the quantized schedules rests on this file: a variant of the step is written here once.
+#pragma once
+
+#include "edt_common.h"
+
+namespace {
+
+template <int V> using Int = std::integral_constant<int, V>;
+template <bool V> using Bool = std::integral_constant<bool, V>;
+
+// ---------------------------------------------------------------------------------------
+// grid-stride drivers
+
+// Vector body + scalar tail: f(Int<kVec>, i) over the whole groups of 8 elements of [0, n), then
+// f(Int<1>, i) over the < 8 elements left (N == kVec); N == 1: f(Int<1>, i) over every element
+// (operands that are not all 16-byte aligned).
+template <int N, class F>
+__device__ __forceinline__ void for_vec_tail(uint64_t n, F&& f) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if constexpr (N == kVec) {
+        const uint64_t nv = n / kVec;
+        for (uint64_t v = tid; v < nv; v += stride) f(Int<kVec>{}, v * kVec);
+        const uint64_t t = nv * kVec + tid;      // scalar tail (< 8 elements)
+        if (t < n) f(Int<1>{}, t);
+    } else {
+        for (uint64_t e = tid; e < n; e += stride) f(Int<1>{}, e);
+    }
+}
+
+// Whole waves only: f(i) for every group of 8 elements of [0, n). The quantizing kernels shuffle
+// across the 4 lanes of a block and the 16 lanes of a scale dword, so no lane of a wave may leave
+// the loop alone: n % 512 == 0 (the entries check it), hence a wave is in or out as a whole.
+template <class F>
+__device__ __forceinline__ void for_whole_waves(uint64_t n, F&& f) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t nv = n / kVec;
+    for (uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x; v < nv; v += stride) f(v * kVec);
+}
+
+// ---------------------------------------------------------------------------------------
+// the step's shared bodies
+
+// acc += round(round(w_k - g) / K_total) for worker k of the launch, each op in the precision of
+// GDT (EDT_LM/diloco.py:243-246): w_k is a.wp(k)'s N elements at i, g the base. a: the launch's
+// argument block (wp, kdiv, kinv). DIV = 1: true division by a.kdiv (torch CPU `delta /
+// num_models`); DIV = 0: multiply by a.kinv = 1/K_total, bit-identical when K_total is a power of
+// two. ROUND_ACC: acc is kept in GDT (rounded after every add); without it the rounded quotients
+// are summed in fp32 (the sharded partials).
+// The loop over k (KC unrolled, else `unroll 4`) stays with the two callers: a loop counter declared
+// in an inlined callee is promoted to a register before the caller's acc, the loop's phi order
+// flips, and the generic-K kernels' register allocation moves with it (spills, lost occupancy).
+template <int GDT, int WDT, int DIV, int N, int H2, bool ROUND_ACC, class A>
+__device__ __forceinline__ void add_delta(const A& a, int k, const float (&g)[N], float (&acc)[N], uint64_t i) {
+    float w[N];
+    ld<WDT, N, nt_worker_loads<WDT, H2>(), H2>(a.wp(k), i, w);
+#pragma unroll
+    for (int j = 0; j < N; ++j) w[j] = w[j] - g[j];              // trained - base
+    rnd<GDT>(w);
+    if constexpr (DIV) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = w[j] / a.kdiv;        // delta / num_models
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = w[j] * a.kinv;
+    }
+    rnd<GDT>(w);
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = acc[j] + w[j];          // acc += delta / K
+    if constexpr (ROUND_ACC) rnd<GDT>(acc);
+}
+
+// a = ((p_0 + p_1) + ...) + p_{np-1} in fp32: the per-rank partials of one shard summed in rank
+// order (one fixed order whatever the collective library does). ld_rank(r, x) loads rank r's N
+// values: an fp32 ld, or ld_q of a packed region.
+template <int N, class LD>
+__device__ __forceinline__ void rank_sum(int np, float (&a)[N], LD&& ld_rank) {
+    ld_rank(0, a);
+    for (int r = 1; r < np; ++r) {
+        float x[N];
+        ld_rank(r, x);
+#pragma unroll
+        for (int j = 0; j < N; ++j) a[j] = a[j] + x[j];
+    }
+}
+
+// The sharded step's phase 2 for the N elements at i: grad = -round_g(rank_sum), then torch's SGD
+// step. g0 = theta as loaded, g = theta after the step (in registers: the caller stores g, or the
+// update g - g0); the momentum is updated in place.
+template <int GDT, int N, class LD>
+__device__ __forceinline__ void sgd_from_sum(const void* theta, void* mom, uint64_t i, const SgdScalars& s, int np,
+                                             LD&& ld_rank, float (&g0)[N], float (&g)[N]) {
+    float a[N], grad[N], b_in[N];
+    ld<GDT, N>(theta, i, g0);
+    ld_momentum<GDT, N>(mom, i, s, b_in);
+    rank_sum(np, a, ld_rank);
+    rnd<GDT>(a);
+#pragma unroll
+    for (int j = 0; j < N; ++j) { grad[j] = -a[j]; g[j] = g0[j]; }   // p.grad = -avg_delta
+    sgd_update<GDT, N>(g, grad, mom, i, s, b_in);
+}
+
+// ---------------------------------------------------------------------------------------
+// host dispatch: a runtime code picks the compile-time tag the generic lambda f is called with
+// (the entries have validated the codes), so a launch site is one nested call
+
+template <class F>
+int with_pair(int gdt, int wdt, F&& f) {            // (master, worker) dtype: valid_pair's three
+    if (gdt == EDT_F32 && wdt == EDT_F32) return f(Int<EDT_F32>{}, Int<EDT_F32>{});
+    if (gdt == EDT_F32) return f(Int<EDT_F32>{}, Int<EDT_BF16>{});
+    return f(Int<EDT_BF16>{}, Int<EDT_BF16>{});
+}
+
+template <class F>
+int with_dtype(int gdt, F&& f) {
+    return gdt == EDT_F32 ? f(Int<EDT_F32>{}) : f(Int<EDT_BF16>{});
+}
+
+template <class F>
+int with_fmt(int fmt, F&& f) {
+    return fmt == EDT_MXFP8 ? f(Int<EDT_MXFP8>{}) : f(Int<EDT_MXFP4>{});
+}
+
+template <class F>
+int with_bool(bool b, F&& f) {
+    return b ? f(Bool<true>{}) : f(Bool<false>{});
+}
+
+// (KC, DIV): compile-time worker counts for the common populations of a table, else the generic
+// loop (KC = 0, also what K = 0 asks for); the divisor is K_total. KC_FUSED (the fused and list
+// kernels): 1, 2, 4, 8 with the multiply, 3 with the division; KC_QUANT (the quantized partial): 8.
+enum { KC_QUANT = 0, KC_FUSED = 1 };
+template <int TABLE, class F>
+int with_kc_div(int K, bool div_exact, F&& f) {
+    if constexpr (TABLE == KC_FUSED) {
+        if (K == 1 && !div_exact) return f(Int<1>{}, Int<0>{});
+        if (K == 2 && !div_exact) return f(Int<2>{}, Int<0>{});
+        if (K == 3 && div_exact) return f(Int<3>{}, Int<1>{});
+        if (K == 4 && !div_exact) return f(Int<4>{}, Int<0>{});
+    }
+    if (K == 8 && !div_exact) return f(Int<8>{}, Int<0>{});
+    return div_exact ? f(Int<0>{}, Int<1>{}) : f(Int<0>{}, Int<0>{});
+}
+
+// ---------------------------------------------------------------------------------------
+// host validation shared by the sharded entries (same codes, same messages)
+
+inline int check_master_dtype(int gdt) {
+    if (gdt != EDT_F32 && gdt != EDT_BF16) return fail(EDT_ERR_ARG, "unsupported dtype");
+    return EDT_OK;
+}
+
+inline int check_partial_count(int nacc) {
+    if (nacc < 1 || nacc > EDT_MAX_WORKERS)
+        return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc, EDT_MAX_WORKERS);
+    return EDT_OK;
+}
+
+// the SGD scalars of a shard's step (n != 0), refusing a missing momentum buffer
+inline int shard_sgd(SgdScalars& s, int gdt, double lr, double momentum_coef, int has_momentum, int nesterov,
+                     const void* momentum) {
+    s = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
+    if (s.use_momentum && !momentum) return fail(EDT_ERR_ARG, "momentum buffer is null");
+    return EDT_OK;
+}
+
+// dst[0 .. count) = src[0 .. count), each checked non-null ("<name>[r] is null"); `aligned` is
+// and-ed with their 16-byte alignment
+template <class T, class U>
+int fill_table(T (&dst)[EDT_MAX_WORKERS], const U* const* src, int count, const char* name, bool& aligned) {
+    for (int r = 0; r < count; ++r) {
+        if (!src[r]) return fail(EDT_ERR_ARG, "%s[%d] is null", name, r);
+        dst[r] = static_cast<T>(src[r]);
+        aligned = aligned && aligned16(src[r]);
+    }
+    return EDT_OK;
+}
+
+}  // namespace

@@ -269,120 +269,31 @@ class ShardedOuterSync:
                 "stream_id": 2 * self.rank + encoder, "elem_base": elem_base}
 
     def _step_body(self) -> None:
-        k = self.kernels
-        mom_off = 0
+        """The driver every schedule shares. Per bucket, `_produce_<mode>` launches the bucket's
+        local work (if any) and issues its collectives, all buckets before the first wait, so the
+        traffic of bucket i overlaps the kernels of bucket i + 1. Then, per bucket in order, its
+        handles are waited for and `_consume_<mode>` steps the owned shard [s0, s1) — `mom` is its
+        slice `sl` of the sharded momentum — and returns the handle of the bucket's gather."""
+        produce = getattr(self, "_produce_" + self.mode)
+        consume = getattr(self, "_consume_" + self.mode)
+        works = [produce(b, e) for b, e in self.buckets]
         gathers = []
-        if self.mode == "reduce":
-            # phase 1: local partial sums, reduce-scatter each bucket as soon as it is ready
-            works = []
-            for b, e in self.buckets:
-                self._launch(k.delta_partial, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
-                             self.k_total, self.acc[b:e], False)
-                works.append(self.comm.reduce_scatter(self._acc_out(b, e), self.acc[b:e], async_op=True))
-            # phase 2: SGD on the owned shard, all-gather theta
-            for (b, e), w in zip(self.buckets, works):
+        mom_off = 0
+        for (b, e), ws in zip(self.buckets, works):
+            for w in ws:
                 w.wait()
-                s0, s1 = self._shard(b, e)
-                per = s1 - s0
-                mom = None if self.mom_shard is None else self.mom_shard[mom_off:mom_off + per]
-                self._launch(k.sgd_apply, self.theta_buf[s0:s1], self._acc_out(b, e), mom, self.has_momentum,
-                             self.lr, self.momentum, self.nesterov)
-                mom_off += per
-                gathers.append(self._gather(b, e, s0, s1))
-        elif self.mode == "reduce_ordered":
-            # phase 1: local partials, each bucket's all-to-all as soon as it is ready (the partial
-            # of bucket [b, e) is laid out [dest rank][shard]; it arrives as [src rank][shard])
-            works = []
-            for b, e in self.buckets:
-                self._launch(k.delta_partial, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
-                             self.k_total, self.acc[b:e], False)
-                works.append(self.comm.all_to_all(self.acc_recv[b:e], self.acc[b:e], async_op=True))
-            # phase 2: the owned shard's N partials summed in rank order + SGD, then the all-gather
-            for (b, e), w in zip(self.buckets, works):
-                w.wait()
-                s0, s1 = self._shard(b, e)
-                per = s1 - s0
-                parts = list(self.acc_recv[b:e].view(self.world, per))
-                mom = None if self.mom_shard is None else self.mom_shard[mom_off:mom_off + per]
-                self._launch(self._sgd_sum, self.theta_buf[s0:s1], parts, mom)
-                mom_off += per
-                gathers.append(self._gather(b, e, s0, s1))
-        elif self.mode == "reduce_q":
-            # reduce_ordered with quantized partials: phase 1 writes bucket [b, e) as `world` packed
-            # regions [dest rank][payload | scales] (the fp32 partial stays in registers), the
-            # all-to-all moves the bytes
-            works = []
-            for b, e in self.buckets:
-                per = (e - b) // self.world
-                qb, qe = self._q_bytes(b), self._q_bytes(e)
-                self._launch(k.delta_partial_q, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
-                             self.k_total, self.q_send[qb:qe], per, self.wire_format,
-                             None if self.residual is None else self.residual[b:e], **self._sr(0, b))
-                works.append(self.comm.all_to_all(self.q_recv[qb:qe], self.q_send[qb:qe], async_op=True))
-            # phase 2: the owned shard's N regions dequantized, summed in rank order + SGD
-            for (b, e), w in zip(self.buckets, works):
-                w.wait()
-                s0, s1 = self._shard(b, e)
-                per = s1 - s0
-                regions = list(self.q_recv[self._q_bytes(b):self._q_bytes(e)].view(self.world, self._q_bytes(per)))
-                mom = None if self.mom_shard is None else self.mom_shard[mom_off:mom_off + per]
-                if self.gather_format is None:
-                    self._launch(k.sgd_apply_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
-                                 self.has_momentum, self.lr, self.momentum, self.nesterov)
-                    gathers.append(self._gather(b, e, s0, s1))
-                else:
-                    # phase 2': the quantized update of the owned shard into this rank's slot of
-                    # u_recv (theta untouched), then the all-gather of the packed bytes
-                    gf = self.gather_format
-                    ub, ur = self._q_bytes(b, gf), self._q_bytes(per, gf)
-                    slot = self.u_recv[ub + self.rank * ur:ub + (self.rank + 1) * ur]
-                    res_g = None if self.residual_g is None else self.residual_g[mom_off:mom_off + per]
-                    self._launch(k.sgd_delta_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
-                                 self.has_momentum, self.lr, self.momentum, self.nesterov, slot, gf, res_g,
-                                 **self._sr(1, s0))
-                    src = slot if self.inplace else slot.clone()
-                    gathers.append(self.comm.all_gather(self.u_recv[ub:self._q_bytes(e, gf)], src, async_op=True))
-                mom_off += per
-            if self.gather_format is not None:
-                # phase 3: as each bucket's updates land, every rank adds the same D(q) to its replica
-                for (b, e), g in zip(self.buckets, gathers):
-                    g.wait()
-                    gf = self.gather_format
-                    self._launch(k.apply_delta_q, self.theta_buf[b:e], self.u_recv[self._q_bytes(b, gf):self._q_bytes(e, gf)],
-                                 (e - b) // self.world, gf)
-        else:
-            # phase 1: every bucket's all-to-all, straight from the worker arenas (a worker's
-            # bucket [b, e) is already laid out [dest rank][per]); one collective per local worker
-            works = []
-            for b, e in self.buckets:
-                works.append([self.comm.all_to_all(self.recv[j][b:e], wb[b:e], async_op=True)
-                              for j, wb in enumerate(self.worker_bufs)])
-            # phase 2: as each bucket lands, the single-GPU fused step on the owned shard
-            for (b, e), ws in zip(self.buckets, works):
-                for w in ws:
-                    w.wait()
-                per = (e - b) // self.world
-                rv = [r[b:e].view(self.world, per) for r in self.recv]
-                # global worker k = src * K_local + j: the reference's worker order
-                shards = [rv[j][src] for src in range(self.world) for j in range(self.k_local)]
-                s0, s1 = self._shard(b, e)
-                mom = None if self.mom_shard is None else self.mom_shard[mom_off:mom_off + per]
-                # broadcast="workers": the HIP kernel also stores the new shard, rounded to the
-                # worker dtype, into local worker 0's arena (its bucket has been sent) — the
-                # rounding copy fused into the step
-                fused = self.broadcast == "workers" and k is _ops and self.tail_bits is None
-                if self.tail_bits is not None:     # shards start at multiples of 64: whole bytes
-                    import functools
-                    fn = functools.partial(k.outer_step, tail_bits=self.tail_bits[s0 // 8:(s1 + 7) // 8])
-                else:
-                    fn = k.outer_step
-                self._launch(fn, self.theta_buf[s0:s1], shards, mom, self.has_momentum, self.lr,
-                             self.momentum, self.nesterov, *([[self.worker_bufs[0][s0:s1]]] if fused else []))
-                mom_off += per
-                if self.broadcast == "workers":
-                    gathers.append(self._gather_to_workers(b, e, s0, s1, rounded=fused))
-                else:
-                    gathers.append(self._gather(b, e, s0, s1))
+            s0, s1 = self._shard(b, e)
+            sl = slice(mom_off, mom_off + (s1 - s0))
+            mom = None if self.mom_shard is None else self.mom_shard[sl]
+            gathers.append(consume(b, e, s0, s1, mom, sl))
+            mom_off = sl.stop
+        if self.mode == "reduce_q" and self.gather_format is not None:
+            # phase 3: as each bucket's updates land, every rank adds the same D(q) to its replica
+            gf = self.gather_format
+            for (b, e), g in zip(self.buckets, gathers):
+                g.wait()
+                self._launch(self.kernels.apply_delta_q, self.theta_buf[b:e],
+                             self.u_recv[self._q_bytes(b, gf):self._q_bytes(e, gf)], (e - b) // self.world, gf)
         for g in gathers:
             g.wait()
         if self.broadcast == "workers":
@@ -390,6 +301,86 @@ class ShardedOuterSync:
                 w.copy_(self.worker_bufs[0])
         if self.momentum:
             self.has_momentum = True
+
+    def _partial(self, b, e):
+        """Phase 1 of the fp32 reduce schedules: the local workers' partial sum of bucket [b, e)."""
+        self._launch(self.kernels.delta_partial, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
+                     self.k_total, self.acc[b:e], False)
+
+    # reduce: reduce-scatter each bucket's partial as soon as it is ready; SGD on the owned shard
+    def _produce_reduce(self, b, e):
+        self._partial(b, e)
+        return [self.comm.reduce_scatter(self._acc_out(b, e), self.acc[b:e], async_op=True)]
+
+    def _consume_reduce(self, b, e, s0, s1, mom, sl):
+        self._launch(self.kernels.sgd_apply, self.theta_buf[s0:s1], self._acc_out(b, e), mom, self.has_momentum,
+                     self.lr, self.momentum, self.nesterov)
+        return self._gather(b, e, s0, s1)
+
+    # reduce_ordered: the partial of bucket [b, e) is laid out [dest rank][shard]; the all-to-all
+    # delivers it as [src rank][shard], and the owned shard's N partials are summed in rank order
+    def _produce_reduce_ordered(self, b, e):
+        self._partial(b, e)
+        return [self.comm.all_to_all(self.acc_recv[b:e], self.acc[b:e], async_op=True)]
+
+    def _consume_reduce_ordered(self, b, e, s0, s1, mom, sl):
+        self._launch(self._sgd_sum, self.theta_buf[s0:s1], list(self.acc_recv[b:e].view(self.world, s1 - s0)), mom)
+        return self._gather(b, e, s0, s1)
+
+    # reduce_q: reduce_ordered with quantized partials: phase 1 writes bucket [b, e) as `world`
+    # packed regions [dest rank][payload | scales] (the fp32 partial stays in registers), the
+    # all-to-all moves the bytes; phase 2 dequantizes the owned shard's N regions
+    def _produce_reduce_q(self, b, e):
+        qb, qe = self._q_bytes(b), self._q_bytes(e)
+        self._launch(self.kernels.delta_partial_q, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
+                     self.k_total, self.q_send[qb:qe], (e - b) // self.world, self.wire_format,
+                     None if self.residual is None else self.residual[b:e], **self._sr(0, b))
+        return [self.comm.all_to_all(self.q_recv[qb:qe], self.q_send[qb:qe], async_op=True)]
+
+    def _consume_reduce_q(self, b, e, s0, s1, mom, sl):
+        k, per = self.kernels, s1 - s0
+        regions = list(self.q_recv[self._q_bytes(b):self._q_bytes(e)].view(self.world, self._q_bytes(per)))
+        if self.gather_format is None:
+            self._launch(k.sgd_apply_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
+                         self.has_momentum, self.lr, self.momentum, self.nesterov)
+            return self._gather(b, e, s0, s1)
+        # phase 2': the quantized update of the owned shard into this rank's slot of u_recv (theta
+        # untouched), then the all-gather of the packed bytes
+        gf = self.gather_format
+        ub, ur = self._q_bytes(b, gf), self._q_bytes(per, gf)
+        slot = self.u_recv[ub + self.rank * ur:ub + (self.rank + 1) * ur]
+        res_g = None if self.residual_g is None else self.residual_g[sl]
+        self._launch(k.sgd_delta_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
+                     self.has_momentum, self.lr, self.momentum, self.nesterov, slot, gf, res_g, **self._sr(1, s0))
+        src = slot if self.inplace else slot.clone()
+        return self.comm.all_gather(self.u_recv[ub:self._q_bytes(e, gf)], src, async_op=True)
+
+    # exact: every bucket's all-to-all straight from the worker arenas (a worker's bucket [b, e) is
+    # already laid out [dest rank][per]), one collective per local worker; as each bucket lands,
+    # the single-GPU fused step on the owned shard
+    def _produce_exact(self, b, e):
+        return [self.comm.all_to_all(self.recv[j][b:e], wb[b:e], async_op=True)
+                for j, wb in enumerate(self.worker_bufs)]
+
+    def _consume_exact(self, b, e, s0, s1, mom, sl):
+        k = self.kernels
+        rv = [r[b:e].view(self.world, s1 - s0) for r in self.recv]
+        # global worker k = src * K_local + j: the reference's worker order
+        shards = [rv[j][src] for src in range(self.world) for j in range(self.k_local)]
+        # broadcast="workers": the HIP kernel also stores the new shard, rounded to the worker
+        # dtype, into local worker 0's arena (its bucket has been sent) — the rounding copy fused
+        # into the step
+        fused = self.broadcast == "workers" and k is _ops and self.tail_bits is None
+        if self.tail_bits is not None:     # shards start at multiples of 64: whole bytes
+            import functools
+            fn = functools.partial(k.outer_step, tail_bits=self.tail_bits[s0 // 8:(s1 + 7) // 8])
+        else:
+            fn = k.outer_step
+        self._launch(fn, self.theta_buf[s0:s1], shards, mom, self.has_momentum, self.lr,
+                     self.momentum, self.nesterov, *([[self.worker_bufs[0][s0:s1]]] if fused else []))
+        if self.broadcast == "workers":
+            return self._gather_to_workers(b, e, s0, s1, rounded=fused)
+        return self._gather(b, e, s0, s1)
 
     def _sgd_sum(self, theta, parts, mom):
         """SGD from the shard's per-rank partials, summed in rank order."""

@@ -38,8 +38,7 @@ def outer_step(theta: torch.Tensor, workers: list[torch.Tensor], momentum: torch
     for w in workers:
         if w.numel() != n or w.dtype != workers[0].dtype:
             raise L.EdtError("every worker buffer must match theta's size and share one dtype")
-    if momentum is not None and (momentum.numel() != n or momentum.dtype != theta.dtype):
-        raise L.EdtError("momentum must have theta's size and dtype")
+    _check_momentum(momentum, theta)
     if broadcast and any(b.numel() != n or b.dtype != workers[0].dtype for b in broadcast):
         raise L.EdtError("broadcast buffers must match theta's size and the workers' dtype")
     if tail_bits is not None:
@@ -190,6 +189,32 @@ def sgd_apply_sum(theta: torch.Tensor, accs: list[torch.Tensor], momentum: torch
                                   L.stream_ptr(theta.device)), "edt_sgd_apply_sum")
 
 
+# Argument checks the sharded wrappers share: one message each, whichever wrapper raises it.
+def _check_momentum(momentum, theta: torch.Tensor) -> None:
+    if momentum is not None and (momentum.numel() != theta.numel() or momentum.dtype != theta.dtype):
+        raise L.EdtError("momentum must have theta's size and dtype")
+
+
+def _check_residual(residual, n: int) -> None:
+    if residual is not None and (residual.dtype != torch.float32 or residual.numel() != n):
+        raise L.EdtError("residual must be a float32 buffer of theta's size")
+
+
+def _check_packed(packed: torch.Tensor, n: int, region_elems: int, fmt) -> None:
+    if region_elems <= 0 or region_elems % 512 or n % region_elems:
+        raise L.EdtError(f"region_elems {region_elems}: a multiple of 512 that divides theta's size {n}")
+    if packed.dtype != torch.uint8 or packed.numel() != n // region_elems * q_region_bytes(region_elems, fmt):
+        raise L.EdtError("packed: a uint8 buffer of theta.numel() / region_elems regions of q_region_bytes each")
+
+
+def _check_regions(regions, n: int, fmt) -> None:
+    if n % 512:
+        raise L.EdtError(f"theta's size {n} is not a multiple of 512 (one region)")
+    rb = q_region_bytes(n, fmt)
+    if not regions or any(r.dtype != torch.uint8 or r.numel() != rb for r in regions):
+        raise L.EdtError(f"regions: uint8 buffers of {rb} bytes (q_region_bytes of theta's size)")
+
+
 QFMT = {"mxfp8": L.EDT_MXFP8, "mxfp4": L.EDT_MXFP4}
 
 
@@ -244,21 +269,15 @@ def delta_partial_q(theta: torch.Tensor, workers: list[torch.Tensor], k_total: i
         if w.numel() != n or w.dtype != workers[0].dtype:
             raise L.EdtError("every worker buffer must match theta's size and share one dtype")
     code = _qfmt(fmt)
-    if region_elems <= 0 or region_elems % 512 or n % region_elems:
-        raise L.EdtError(f"region_elems {region_elems}: a multiple of 512 that divides theta's size {n}")
-    if packed.dtype != torch.uint8 or packed.numel() != n // region_elems * q_region_bytes(region_elems, fmt):
-        raise L.EdtError("packed: a uint8 buffer of theta.numel() / region_elems regions of q_region_bytes each")
-    if residual is not None and (residual.dtype != torch.float32 or residual.numel() != n):
-        raise L.EdtError("residual must be a float32 buffer of theta's size")
+    _check_packed(packed, n, region_elems, fmt)
+    _check_residual(residual, n)
+    head = (L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers), L.dtype_code(workers[0]), len(workers),
+            int(k_total), n, int(region_elems), code)
     if sr:
-        L.check(lib.edt_delta_partial_q_sr(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
-                                           L.dtype_code(workers[0]), len(workers), int(k_total), n, int(region_elems),
-                                           code, L.ptr(packed), int(seed), int(step), int(stream_id), int(elem_base),
+        L.check(lib.edt_delta_partial_q_sr(*head, L.ptr(packed), int(seed), int(step), int(stream_id), int(elem_base),
                                            L.stream_ptr(theta.device)), "edt_delta_partial_q_sr")
         return
-    L.check(lib.edt_delta_partial_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
-                                    L.dtype_code(workers[0]), len(workers), int(k_total), n, int(region_elems), code,
-                                    L.ptr(residual), L.ptr(packed), L.stream_ptr(theta.device)),
+    L.check(lib.edt_delta_partial_q(*head, L.ptr(residual), L.ptr(packed), L.stream_ptr(theta.device)),
             "edt_delta_partial_q")
 
 
@@ -271,13 +290,8 @@ def sgd_apply_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt, momen
     L.require_device(theta, momentum, *regions)
     n = theta.numel()
     code = _qfmt(fmt)
-    if n % 512:
-        raise L.EdtError(f"theta's size {n} is not a multiple of 512 (one region)")
-    rb = q_region_bytes(n, fmt)
-    if not regions or any(r.dtype != torch.uint8 or r.numel() != rb for r in regions):
-        raise L.EdtError(f"regions: uint8 buffers of {rb} bytes (q_region_bytes of theta's size)")
-    if momentum is not None and (momentum.numel() != n or momentum.dtype != theta.dtype):
-        raise L.EdtError("momentum must have theta's size and dtype")
+    _check_regions(regions, n, fmt)
+    _check_momentum(momentum, theta)
     L.check(lib.edt_sgd_apply_sum_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code,
                                     L.ptr(momentum), int(has_momentum), n, float(lr), float(momentum_coef),
                                     int(nesterov), L.stream_ptr(theta.device)), "edt_sgd_apply_sum_q")
@@ -299,28 +313,19 @@ def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, mo
     L.require_device(theta, momentum, packed_out, residual, *regions)
     n = theta.numel()
     code_in, code_out = _qfmt(fmt_in), _qfmt(fmt_out)
-    if n % 512:
-        raise L.EdtError(f"theta's size {n} is not a multiple of 512 (one region)")
-    rb = q_region_bytes(n, fmt_in)
-    if not regions or any(r.dtype != torch.uint8 or r.numel() != rb for r in regions):
-        raise L.EdtError(f"regions: uint8 buffers of {rb} bytes (q_region_bytes of theta's size)")
-    if momentum is not None and (momentum.numel() != n or momentum.dtype != theta.dtype):
-        raise L.EdtError("momentum must have theta's size and dtype")
+    _check_regions(regions, n, fmt_in)
+    _check_momentum(momentum, theta)
     if packed_out.dtype != torch.uint8 or packed_out.numel() != q_region_bytes(n, fmt_out):
         raise L.EdtError("packed_out: a uint8 buffer of q_region_bytes(theta's size, fmt_out)")
-    if residual is not None and (residual.dtype != torch.float32 or residual.numel() != n):
-        raise L.EdtError("residual must be a float32 buffer of theta's size")
+    _check_residual(residual, n)
+    head = (L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code_in, L.ptr(momentum),
+            int(has_momentum), n, float(lr), float(momentum_coef), int(nesterov))
     if sr:
-        L.check(lib.edt_sgd_delta_sum_q_sr(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions),
-                                           code_in, L.ptr(momentum), int(has_momentum), n, float(lr),
-                                           float(momentum_coef), int(nesterov), L.ptr(packed_out), code_out, int(seed),
-                                           int(step), int(stream_id), int(elem_base), L.stream_ptr(theta.device)),
-                "edt_sgd_delta_sum_q_sr")
+        L.check(lib.edt_sgd_delta_sum_q_sr(*head, L.ptr(packed_out), code_out, int(seed), int(step), int(stream_id),
+                                           int(elem_base), L.stream_ptr(theta.device)), "edt_sgd_delta_sum_q_sr")
         return
-    L.check(lib.edt_sgd_delta_sum_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code_in,
-                                    L.ptr(momentum), int(has_momentum), n, float(lr), float(momentum_coef),
-                                    int(nesterov), L.ptr(residual), L.ptr(packed_out), code_out,
-                                    L.stream_ptr(theta.device)), "edt_sgd_delta_sum_q")
+    L.check(lib.edt_sgd_delta_sum_q(*head, L.ptr(residual), L.ptr(packed_out), code_out, L.stream_ptr(theta.device)),
+            "edt_sgd_delta_sum_q")
 
 
 def apply_delta_q(theta: torch.Tensor, packed: torch.Tensor, region_elems: int, fmt) -> None:
@@ -331,10 +336,7 @@ def apply_delta_q(theta: torch.Tensor, packed: torch.Tensor, region_elems: int, 
     L.require_device(theta, packed)
     n = theta.numel()
     code = _qfmt(fmt)
-    if region_elems <= 0 or region_elems % 512 or n % region_elems:
-        raise L.EdtError(f"region_elems {region_elems}: a multiple of 512 that divides theta's size {n}")
-    if packed.dtype != torch.uint8 or packed.numel() != n // region_elems * q_region_bytes(region_elems, fmt):
-        raise L.EdtError("packed: a uint8 buffer of theta.numel() / region_elems regions of q_region_bytes each")
+    _check_packed(packed, n, region_elems, fmt)
     L.check(lib.edt_apply_delta_q(L.ptr(theta), L.dtype_code(theta), L.ptr(packed), n, int(region_elems), code,
                                   L.stream_ptr(theta.device)), "edt_apply_delta_q")
 

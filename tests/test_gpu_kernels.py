@@ -909,3 +909,26 @@ def test_sgd_apply_sum_vs_oracle(oracle, dev, ops, gdt, nacc, off):
     th, m = theta[off:].clone(), mom[off:].clone()
     oracle.sgd_apply(th, total, m, True, 0.7, 0.9, True)
     assert torch.equal(bits(th_d.cpu()), bits(th)) and torch.equal(bits(m_d.cpu()), bits(m))
+
+
+@pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("off", [0, 1])
+@pytest.mark.parametrize("mu,nesterov", [(0.9, True), (0.0, False)])
+def test_sgd_apply_is_sum_of_one(dev, ops, gdt, off, mu, nesterov):
+    """edt_sgd_apply and edt_sgd_apply_sum with one partial run the same step (the np == 1 case of
+    the shared sum -> SGD tail): theta, the momentum and theta after a second step (carried
+    momentum) equal bit for bit. n = 512 + 8 + 3: vector body plus scalar tail; off = 1 slices every
+    operand from element 1, so they are misaligned and the scalar kernel runs."""
+    n = 512 + 8 + 3
+    g = torch.Generator().manual_seed(7)
+    theta = (torch.randn(n + 1, generator=g) * 0.02).to(gdt).to(dev)
+    mom = torch.zeros(n + 1, dtype=gdt, device=dev)
+    accs = [(torch.randn(n + 1, generator=g) * 1e-3).to(dev) for _ in range(2)]
+    th_a, m_a, th_b, m_b = theta.clone()[off:off + n], mom.clone()[off:off + n], theta.clone()[off:off + n], mom.clone()[off:off + n]
+    for step, acc in enumerate(accs):
+        ops.sgd_apply(th_a, acc[off:off + n], m_a if mu else None, step > 0, 0.7, mu, nesterov)
+        ops.sgd_apply_sum(th_b, [acc[off:off + n]], m_b if mu else None, step > 0, 0.7, mu, nesterov)
+        assert torch.equal(bits(th_a.cpu()), bits(th_b.cpu())), f"theta differs after step {step + 1}"
+        assert torch.equal(bits(m_a.cpu()), bits(m_b.cpu())), f"momentum differs after step {step + 1}"
+    assert not torch.equal(bits(th_a.cpu()), bits(theta[off:off + n].cpu()))
+    assert bool(m_a.cpu().float().abs().sum() > 0) == bool(mu)
