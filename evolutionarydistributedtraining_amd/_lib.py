@@ -51,6 +51,8 @@ SIGNATURES = [
     ("edt_sgd_apply_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_sgd_delta_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _P, _I, _P]),
     ("edt_apply_delta_q", _I, [_P, _I, _P, _U64, _U64, _I, _P]),
+    ("edt_apply_delta_q_bcast", _I, [_P, _I, _P, _U64, _U64, _I, ctypes.POINTER(_P), _I, _I, _P]),
+    ("edt_broadcast_theta", _I, [_P, _I, _U64, ctypes.POINTER(_P), _I, _I, _P]),
     ("edt_delta_partial_q_sr", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _U64, _I, _P, _U64, _U64,
                                     ctypes.c_uint32, _U64, _P]),
     ("edt_sgd_delta_sum_q_sr", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _I, _U64, _U64,

@@ -294,6 +294,20 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void probe_kernel(OuterArgs 
 }
 
 
+// The broadcast of EDT_LM/diloco.py:302-308 on its own (edt_broadcast_theta): theta is read once and
+// round_w(theta) stored to every destination — outer_elems' BC stores for the sharded schedules whose
+// new theta arrives through the all-gather, so no local kernel holds it in registers. A pure
+// stream: one 16-byte load per lane (two for fp32), then d.n stores of the same registers.
+template <int GDT, int WDT, int N>
+__global__ __launch_bounds__(kBlock) void broadcast_theta_kernel(const void* theta, uint64_t n, BcastDst d) {
+    for_vec_tail<N>(n, [&](auto V, uint64_t i) {
+        constexpr int M = decltype(V)::value;
+        float g[M];
+        ld<GDT, M>(theta, i, g);
+        st_bcast<WDT, M>(d, i, g);
+    });
+}
+
 // ---------------------------------------------------------------------------------------
 // launch helpers
 
@@ -456,6 +470,27 @@ int edt_outer_step_bcast(void* theta_g, int gdt, const void* const* theta_k, int
     if (n == 0) return EDT_OK;
     for (int k = 0; k < nbcast; ++k) vec = vec && aligned16(bcast[k]);
     return launch_outer<MODE_FUSED, true>(gdt, wdt, a, vec, (hipStream_t)stream);
+}
+
+int edt_broadcast_theta(const void* theta_g, int gdt, uint64_t n, void* const* bcast, int wdt, int nbcast,
+                        void* stream) {
+    g_err[0] = 0;
+    if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
+    if (int rc = check_bcast_count(nbcast)) return rc;
+    if (n == 0 || nbcast == 0) return EDT_OK;
+    if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
+    bool vec = aligned16(theta_g);
+    BcastDst d;
+    if (int rc = fill_bcast(d, bcast, nbcast, n, wdt, theta_g, n * (gdt == EDT_BF16 ? 2 : 4), nullptr, 0, vec)) return rc;
+    const unsigned g = grid_for(n, vec);
+    hipStream_t s = (hipStream_t)stream;
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_bool(vec, [&](auto V) {
+            broadcast_theta_kernel<decltype(G)::value, decltype(W)::value, decltype(V)::value ? kVec : 1>
+                <<<g, kBlock, 0, s>>>(theta_g, n, d);
+            return check_launch("broadcast_theta_kernel");
+        });
+    });
 }
 
 int edt_outer_step_ws(void* theta_g, int gdt, const void* const* theta_k, int wdt, int K, void* momentum,

@@ -353,10 +353,15 @@ __global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_sr_kernel(const void* 
     delta_sum_q_body<GDT, FIN, FOUT, false, EDT_ROUND_STOCHASTIC>(theta, P, np, mom, n, s, nullptr, packed_out, sr);
 }
 
-// phase 3: theta <- round_g(theta + D(q)) over a bucket of n / region_elems regions back to back
-template <int GDT, int FMT>
+// phase 3: theta <- round_g(theta + D(q)) over a bucket of n / region_elems regions back to back.
+// BC (edt_apply_delta_q_bcast): the value written to theta also goes, rounded to WDT, to every
+// destination of bc — the local workers' refresh in the pass that already holds the new theta in
+// registers. A destination element is written by the thread that wrote theta's, and nothing here
+// reads a destination.
+template <int GDT, int FMT, int WDT = GDT, bool BC = false>
 __global__ __launch_bounds__(kBlock) void apply_delta_q_kernel(void* theta, const uint8_t* packed, uint64_t n,
-                                                               uint64_t tiles_per_region, uint64_t region_bytes) {
+                                                               uint64_t tiles_per_region, uint64_t region_bytes,
+                                                               std::conditional_t<BC, BcastDst, NoBcast> bc) {
     for_whole_waves(n, [&](uint64_t i) {
         const RegionOf r = region_of(i, tiles_per_region);
         float g[kVec], d[kVec];
@@ -366,6 +371,7 @@ __global__ __launch_bounds__(kBlock) void apply_delta_q_kernel(void* theta, cons
         for (int j = 0; j < kVec; ++j) g[j] = g[j] + d[j];
         rnd<GDT>(g);
         st<GDT, kVec>(theta, i, g);
+        if constexpr (BC) st_bcast<WDT, kVec>(bc, i, g);
     });
 }
 
@@ -583,27 +589,55 @@ int edt_sgd_delta_sum_q_sr(const void* theta_g, int gdt, const void* const* regi
                                 nesterov, nullptr, packed_out, fmt_out, &sr, elem_base, stream);
 }
 
-int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
-                      void* stream) {
-    g_err[0] = 0;
+// edt_apply_delta_q (nbcast = 0: bcast and wdt unused) and edt_apply_delta_q_bcast: one validation
+static int apply_delta_q_impl(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
+                              void* const* bcast, int wdt, int nbcast, void* stream) {
     if (int rc = check_master_dtype(gdt)) return rc;
     if (int rc = check_fmt(fmt)) return rc;
     if (int rc = check_regions(n, region_elems)) return rc;
     if (n == 0) return EDT_OK;
     if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
     if (!packed) return fail(EDT_ERR_ARG, "packed is null");
-    if (!aligned16(theta_g) || !aligned16(packed))
-        return fail(EDT_ERR_ARG, "the quantized update needs 16-byte aligned operands");
+    const uint64_t tpr = region_elems / 512, rb = edt_q_region_bytes(region_elems, fmt);
+    bool al = aligned16(theta_g) && aligned16(packed);
+    BcastDst bc;
+    if (nbcast > 0)
+        if (int rc = fill_bcast(bc, bcast, nbcast, n, wdt, theta_g, n * (gdt == EDT_BF16 ? 2 : 4), packed,
+                                n / region_elems * rb, al))
+            return rc;
+    if (!al) return fail(EDT_ERR_ARG, "the quantized update needs 16-byte aligned operands");
     const unsigned g = grid_for(n, true);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t* q = static_cast<const uint8_t*>(packed);
-    const uint64_t tpr = region_elems / 512, rb = edt_q_region_bytes(region_elems, fmt);
+    if (nbcast > 0)
+        return with_pair(gdt, wdt, [&](auto G, auto W) {
+            return with_fmt(fmt, [&](auto F) {
+                apply_delta_q_kernel<decltype(G)::value, decltype(F)::value, decltype(W)::value, true>
+                    <<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb, bc);
+                return check_launch("apply_delta_q_kernel");
+            });
+        });
     return with_dtype(gdt, [&](auto G) {
         return with_fmt(fmt, [&](auto F) {
-            apply_delta_q_kernel<decltype(G)::value, decltype(F)::value><<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb);
+            apply_delta_q_kernel<decltype(G)::value, decltype(F)::value>
+                <<<g, kBlock, 0, st>>>(theta_g, q, n, tpr, rb, NoBcast{});
             return check_launch("apply_delta_q_kernel");
         });
     });
+}
+
+int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
+                      void* stream) {
+    g_err[0] = 0;
+    return apply_delta_q_impl(theta_g, gdt, packed, n, region_elems, fmt, nullptr, gdt, 0, stream);
+}
+
+int edt_apply_delta_q_bcast(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
+                            void* const* bcast, int wdt, int nbcast, void* stream) {
+    g_err[0] = 0;
+    if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
+    if (int rc = check_bcast_count(nbcast)) return rc;
+    return apply_delta_q_impl(theta_g, gdt, packed, n, region_elems, fmt, bcast, wdt, nbcast, stream);
 }
 
 }  // extern "C"

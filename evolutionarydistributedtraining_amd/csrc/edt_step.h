@@ -104,6 +104,23 @@ __device__ __forceinline__ void sgd_from_sum(const void* theta, void* mom, uint6
     sgd_update<GDT, N>(g, grad, mom, i, s, b_in);
 }
 
+// The destinations of a broadcast fused into a pass over theta (edt_apply_delta_q_bcast,
+// edt_broadcast_theta): n worker arenas of one dtype. NoBcast is what a kernel without the
+// broadcast takes in its place (no bytes).
+struct BcastDst {
+    void* p[EDT_MAX_WORKERS];
+    int n;
+};
+struct NoBcast {};
+
+// x (the N values just written to theta at i, in registers) rounded to WDT (RNE, torch copy_) into
+// every destination: the stores of outer_elems' BC branch, under the same EDT_NT_STORES policy.
+template <int WDT, int N>
+__device__ __forceinline__ void st_bcast(const BcastDst& d, uint64_t i, const float (&x)[N]) {
+#pragma unroll 4
+    for (int k = 0; k < d.n; ++k) st<WDT, N, (EDT_NT_STORES != 0)>(d.p[k], i, x);
+}
+
 // ---------------------------------------------------------------------------------------
 // host dispatch: a runtime code picks the compile-time tag the generic lambda f is called with
 // (the entries have validated the codes), so a launch site is one nested call
@@ -177,6 +194,37 @@ int fill_table(T (&dst)[EDT_MAX_WORKERS], const U* const* src, int count, const 
         dst[r] = static_cast<T>(src[r]);
         aligned = aligned && aligned16(src[r]);
     }
+    return EDT_OK;
+}
+
+inline int check_bcast_count(int nbcast) {
+    if (nbcast < 0 || nbcast > EDT_MAX_WORKERS)
+        return fail(EDT_ERR_ARG, "broadcast count %d out of range [0, %d]", nbcast, EDT_MAX_WORKERS);
+    return EDT_OK;
+}
+
+inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// d = bcast[0 .. nbcast) (nbcast >= 1, n != 0 elements of wdt each): each checked non-null and
+// clear of theta_g's theta_bytes ("bcast[k] overlaps theta_g", as edt_outer_step_bcast reports it)
+// and of `packed`'s packed_bytes (packed may be null: no such operand); `aligned` is and-ed with
+// their 16-byte alignment
+inline int fill_bcast(BcastDst& d, void* const* bcast, int nbcast, uint64_t n, int wdt, const void* theta_g,
+                      uint64_t theta_bytes, const void* packed, uint64_t packed_bytes, bool& aligned) {
+    memset(&d, 0, sizeof(d));
+    if (!bcast) return fail(EDT_ERR_ARG, "bcast is null");
+    const uint64_t bytes = n * (wdt == EDT_BF16 ? 2 : 4);
+    for (int k = 0; k < nbcast; ++k) {
+        if (!bcast[k]) return fail(EDT_ERR_ARG, "bcast[%d] is null", k);
+        if (bytes_overlap(bcast[k], bytes, theta_g, theta_bytes)) return fail(EDT_ERR_ARG, "bcast[%d] overlaps theta_g", k);
+        if (bytes_overlap(bcast[k], bytes, packed, packed_bytes)) return fail(EDT_ERR_ARG, "bcast[%d] overlaps packed", k);
+        d.p[k] = bcast[k];
+        aligned = aligned && aligned16(bcast[k]);
+    }
+    d.n = nbcast;
     return EDT_OK;
 }
 

@@ -54,6 +54,18 @@ on the comm stream overlaps the HBM-bound kernels on the compute stream:
                          (diloco.py:302-308 saves the base to every worker dir; the bf16 workers load
                          it rounded). The fp32 master then stays sharded (`gather_theta()` assembles
                          it on demand, e.g. for a checkpoint). Wire bytes: (N-1)/N * P * (K_local + 1) * b_w.
+  step(broadcast=True)   hands the new theta to the local workers in the step's own pass, for every
+                         schedule that keeps the theta replica: when the step's work completes each
+                         local worker arena over [0, n_pad) holds round_w(theta_new) (RNE, what
+                         `w.copy_(theta)` leaves), and theta, the momentum, the residuals, the packed
+                         buffers and q_step are bit-identical to step(). reduce_q with gather_format
+                         fuses it into phase 3 (edt_apply_delta_q_bcast: the pass already holds the
+                         new theta in registers, + K_local * b_w bytes per element); the others run
+                         one edt_broadcast_theta per bucket as its all-gather lands (theta read
+                         once, + b_g + K_local * b_w), overlapping the later buckets' gathers.
+                         With broadcast="workers" the step already does it and the flag changes
+                         nothing. NaN elements (a scale-255 block) are NaN in theta and in every
+                         worker; their payload bits are not specified.
   mode="auto" / broadcast="auto" (defaults) pick the combination with the fewest wire bytes,
   ties to exact, then reduce_ordered: at K = 8 bf16 workers, fp32 theta: N = 2 reduce_ordered/theta
   (8 B/elem), N = 4 and 8 exact/workers (6 and 4 B/elem); all fp32: N = 2 and 4 reduce_ordered,
@@ -225,10 +237,17 @@ class ShardedOuterSync:
         b.record()
         self.kernel_events.append((a, b))
 
-    def kernel_bytes(self) -> int:
+    def kernel_bytes(self, broadcast: bool = False) -> int:
         """Algorithmic HBM bytes of one step's local kernels on this rank (steady state:
         momentum read + written). exact: the fused kernel over the owned shards with all K
-        workers; reduce: the partial over the whole arena + the SGD over the owned shards."""
+        workers; reduce: the partial over the whole arena + the SGD over the owned shards.
+        broadcast: of step(broadcast=True) — the K_local worker arenas written (fused into phase 3
+        of the quantized gather), and theta read once more where edt_broadcast_theta does it."""
+        if broadcast and self.broadcast != "workers":
+            wb = self.worker_bufs[0].element_size()
+            fused = self.mode == "reduce_q" and self.gather_format is not None
+            return self.kernel_bytes() + self.n_pad * (self.k_local * wb
+                                                       + (0 if fused else self.theta_buf.element_size()))
         wb = self.worker_bufs[0].element_size()
         gb = self.theta_buf.element_size()
         shard = self.n_pad // self.world
@@ -253,10 +272,13 @@ class ShardedOuterSync:
         return self.n_pad * (self.k_local * wb + gb + 4) + shard * (4 + 2 * gb + mom)
 
     @traced("edt/ShardedOuterSync.step")
-    def step(self) -> None:
-        """One outer step; returns when the work is enqueued (stream-ordered, async)."""
+    def step(self, broadcast: bool = False) -> None:
+        """One outer step; returns when the work is enqueued (stream-ordered, async).
+        broadcast=True: every local worker arena over [0, n_pad) also holds the new theta rounded
+        to the worker dtype when the step's work completes (module docstring); theta, the momentum,
+        the residuals and q_step are what step() leaves."""
         with trange(f"edt/sharded.{self.mode}/{self.broadcast}"):
-            self._step_body()
+            self._step_body(broadcast)
         self.q_step += 1
 
     def _sr(self, encoder: int, elem_base: int) -> dict:
@@ -268,12 +290,23 @@ class ShardedOuterSync:
         return {"rounding": "stochastic", "seed": self.seed, "step": self.q_step,
                 "stream_id": 2 * self.rank + encoder, "elem_base": elem_base}
 
-    def _step_body(self) -> None:
+    def _step_body(self, broadcast: bool = False) -> None:
         """The driver every schedule shares. Per bucket, `_produce_<mode>` launches the bucket's
         local work (if any) and issues its collectives, all buckets before the first wait, so the
         traffic of bucket i overlaps the kernels of bucket i + 1. Then, per bucket in order, its
         handles are waited for and `_consume_<mode>` steps the owned shard [s0, s1) — `mom` is its
-        slice `sl` of the sharded momentum — and returns the handle of the bucket's gather."""
+        slice `sl` of the sharded momentum — and returns the handle of the bucket's gather.
+
+        broadcast (step(broadcast=True)): as each bucket's gather lands, its slice of every local
+        worker arena is overwritten with round_w(theta_new) on the compute stream — fused into
+        phase 3 where that pass exists, else by one edt_broadcast_theta per bucket while later
+        buckets' gathers are still in flight. The arenas are the step's inputs, so the hazards are:
+        the reduce schedules read them in phase 1 only, and phase 1 of every bucket is enqueued
+        above before any destination store, on the same stream; exact mode's all-to-alls read them
+        on the communicator's stream, and a bucket's all-to-all handles are waited for (before its
+        consume, hence before its gather is issued and waited for) before its arena slice is
+        written. broadcast="workers" already leaves the arenas so: nothing is added."""
+        refresh = broadcast and self.broadcast != "workers"
         produce = getattr(self, "_produce_" + self.mode)
         consume = getattr(self, "_consume_" + self.mode)
         works = [produce(b, e) for b, e in self.buckets]
@@ -290,10 +323,18 @@ class ShardedOuterSync:
         if self.mode == "reduce_q" and self.gather_format is not None:
             # phase 3: as each bucket's updates land, every rank adds the same D(q) to its replica
             gf = self.gather_format
+            fused = refresh and hasattr(self.kernels, "broadcast_theta")
             for (b, e), g in zip(self.buckets, gathers):
                 g.wait()
                 self._launch(self.kernels.apply_delta_q, self.theta_buf[b:e],
-                             self.u_recv[self._q_bytes(b, gf):self._q_bytes(e, gf)], (e - b) // self.world, gf)
+                             self.u_recv[self._q_bytes(b, gf):self._q_bytes(e, gf)], (e - b) // self.world, gf,
+                             **({"broadcast": [w[b:e] for w in self.worker_bufs]} if fused else {}))
+                if refresh and not fused:
+                    self._refresh_workers(b, e)
+        elif refresh:
+            for (b, e), g in zip(self.buckets, gathers):
+                g.wait()
+                self._refresh_workers(b, e)
         for g in gathers:
             g.wait()
         if self.broadcast == "workers":
@@ -301,6 +342,16 @@ class ShardedOuterSync:
                 w.copy_(self.worker_bufs[0])
         if self.momentum:
             self.has_momentum = True
+
+    def _refresh_workers(self, b, e):
+        """Bucket [b, e) of every local worker arena <- round_w(theta) (torch copy_: RNE), theta
+        read once (edt_broadcast_theta); its gather has been waited for."""
+        dst = [w[b:e] for w in self.worker_bufs]
+        if hasattr(self.kernels, "broadcast_theta"):
+            self._launch(self.kernels.broadcast_theta, self.theta_buf[b:e], dst)
+            return
+        for d in dst:                        # stand-in kernels (CPU tests): the same copies in torch
+            d.copy_(self.theta_buf[b:e])
 
     def _partial(self, b, e):
         """Phase 1 of the fp32 reduce schedules: the local workers' partial sum of bucket [b, e)."""

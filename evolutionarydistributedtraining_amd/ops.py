@@ -328,17 +328,58 @@ def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, mo
             "edt_sgd_delta_sum_q")
 
 
-def apply_delta_q(theta: torch.Tensor, packed: torch.Tensor, region_elems: int, fmt) -> None:
+def _check_bcast(theta: torch.Tensor, outs) -> None:
+    """The destinations of a broadcast of theta: flat device tensors of theta's length and of one
+    worker dtype that pairs with theta's (fp32 theta: fp32 or bf16; bf16 theta: bf16)."""
+    n = theta.numel()
+    if any(o.numel() != n or o.dtype != outs[0].dtype for o in outs):
+        raise L.EdtError("broadcast buffers must match theta's size and share one dtype")
+    if outs and (L.dtype_code(theta), L.dtype_code(outs[0])) == (L.EDT_BF16, L.EDT_F32):
+        raise L.EdtError("unsupported dtype pair: a bfloat16 theta broadcasts to bfloat16 workers")
+
+
+def apply_delta_q(theta: torch.Tensor, packed: torch.Tensor, region_elems: int, fmt,
+                  broadcast: list[torch.Tensor] | None = None) -> None:
     """theta = round(theta + D(q)) in place: `packed` (uint8) holds theta.numel() / region_elems
     regions back to back, delta_partial_q's layout (edt_apply_delta_q: the quantized gather's
-    phase 3, run with the same bytes on every rank)."""
+    phase 3, run with the same bytes on every rank).
+    broadcast: flat buffers of one worker dtype, each of theta's length, that receive the new theta
+    rounded to that dtype in the same pass (edt_apply_delta_q_bcast: what `b.copy_(theta)` per
+    buffer would leave, without re-reading theta). Past 64 buffers the launch takes the first 64
+    and broadcast_theta the rest."""
     lib = L.lib()
-    L.require_device(theta, packed)
+    broadcast = list(broadcast or [])
+    L.require_device(theta, packed, *broadcast)
     n = theta.numel()
     code = _qfmt(fmt)
     _check_packed(packed, n, region_elems, fmt)
-    L.check(lib.edt_apply_delta_q(L.ptr(theta), L.dtype_code(theta), L.ptr(packed), n, int(region_elems), code,
-                                  L.stream_ptr(theta.device)), "edt_apply_delta_q")
+    if not broadcast:
+        L.check(lib.edt_apply_delta_q(L.ptr(theta), L.dtype_code(theta), L.ptr(packed), n, int(region_elems), code,
+                                      L.stream_ptr(theta.device)), "edt_apply_delta_q")
+        return
+    _check_bcast(theta, broadcast)
+    head, rest = broadcast[:L.EDT_MAX_WORKERS], broadcast[L.EDT_MAX_WORKERS:]
+    L.check(lib.edt_apply_delta_q_bcast(L.ptr(theta), L.dtype_code(theta), L.ptr(packed), n, int(region_elems), code,
+                                        L.ptr_array(head), L.dtype_code(head[0]), len(head),
+                                        L.stream_ptr(theta.device)), "edt_apply_delta_q_bcast")
+    if rest:
+        broadcast_theta(theta, rest)
+
+
+def broadcast_theta(theta: torch.Tensor, outs: list[torch.Tensor]) -> None:
+    """outs[k].copy_(theta) for every k with theta read once per launch (edt_broadcast_theta: the
+    broadcast of EDT_LM/diloco.py:302-308 for the sharded schedules whose new theta arrives through
+    the all-gather). outs: flat buffers of one worker dtype, each of theta's length, any alignment;
+    more than 64 go in chunks of 64."""
+    lib = L.lib()
+    outs = list(outs)
+    L.require_device(theta, *outs)
+    _check_bcast(theta, outs)
+    for c in range(0, len(outs), L.EDT_MAX_WORKERS):
+        chunk = outs[c:c + L.EDT_MAX_WORKERS]
+        L.check(lib.edt_broadcast_theta(L.ptr(theta), L.dtype_code(theta), theta.numel(), L.ptr_array(chunk),
+                                        L.dtype_code(chunk[0]), len(chunk), L.stream_ptr(theta.device)),
+                "edt_broadcast_theta")
 
 
 def pair_merge(b1: torch.Tensor, b2: torch.Tensor | None, m1: torch.Tensor, m2: torch.Tensor,

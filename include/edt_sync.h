@@ -261,6 +261,26 @@ int edt_sgd_delta_sum_q_sr(const void* theta_g, int gdt, const void* const* regi
 int edt_apply_delta_q(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
                       void* stream);
 
+/* Phase 3 fused with the broadcast of EDT_LM/diloco.py:302-308 (the new global weights handed to
+ * every worker): edt_apply_delta_q's update of theta_g, bit for bit, and in the same pass the value
+ * written to theta_g, rounded to the worker dtype (RNE, torch copy_), is stored into the nbcast
+ * device buffers bcast[0..nbcast) (n elements of wdt each) — what edt_apply_delta_q followed by
+ * nbcast copies (each re-reading theta) leaves. (gdt, wdt) is one of edt_outer_step's dtype pairs;
+ * 0 <= nbcast <= 64, nbcast = 0 is edt_apply_delta_q. A NaN element of theta (a scale-255 block) is
+ * NaN in every destination; its payload bits are not specified. EDT_ERR_ARG as edt_apply_delta_q,
+ * and when a destination is null, not 16-byte aligned, or overlaps theta_g or packed. */
+int edt_apply_delta_q_bcast(void* theta_g, int gdt, const void* packed, uint64_t n, uint64_t region_elems, int fmt,
+                            void* const* bcast, int wdt, int nbcast, void* stream);
+
+/* The broadcast alone, for the schedules whose new theta arrives through the all-gather: theta_g
+ * (n elements of gdt, any n, any alignment) is read once and round_w(theta) (RNE, torch copy_) is
+ * stored into bcast[0..nbcast) (n elements of wdt each) — nbcast device copies in one pass.
+ * Operands that are all 16-byte aligned take 8-element accesses with a scalar tail, others the
+ * scalar path. 0 <= nbcast <= 64 (0: nothing to do). EDT_ERR_ARG for an unsupported dtype pair, a
+ * null pointer or a destination that overlaps theta_g. */
+int edt_broadcast_theta(const void* theta_g, int gdt, uint64_t n, void* const* bcast, int wdt, int nbcast,
+                        void* stream);
+
 /* ---- EDT pairwise merge -------------------------------------------------------------------
  * Replaces EDT_LM/train/crossover.py:150-163 + 166-230 for one child:
  *   B = lerp(0.5, b1, b2)                         (run_linear_merge_5050, in the model dtype wdt)
