@@ -36,6 +36,10 @@ SIGNATURES = [
     ("edt_outer_step_bcast", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I,
                                   ctypes.POINTER(_P), _I, _P]),
     ("edt_outer_step_tail", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _P]),
+    ("edt_outer_step_scaled", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P,
+                                   ctypes.c_float, _P]),
+    ("edt_delta_stats_doubles", _U64, [_I, ctypes.c_int64]),
+    ("edt_delta_stats", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _U64, _P, ctypes.c_int64, _P, _P]),
     ("edt_pair_merge_tail", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _U64, _D, _D, _I, _P, _P]),
     ("edt_outer_step_ws", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _P]),
     ("edt_outer_list_workspace_bytes", _U64, [_I, _I]),

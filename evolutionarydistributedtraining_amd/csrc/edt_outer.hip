@@ -29,6 +29,8 @@ struct OuterArgs {
     Workers w;
     Workers bc;          // broadcast mode: round_w(theta_new) stored to these (worker dtype)
     int nbc;
+    float grad_scale;    // scaled mode (SC): the pseudo-gradient's clip coefficient, last so that no
+                         // other kernel argument moves
     __device__ __forceinline__ const void* wp(int k) const { return w.p[k]; }
 };
 
@@ -59,7 +61,7 @@ enum { MODE_FUSED = 0, MODE_PARTIAL = 1, MODE_CHAIN = 2 };
 // Per-element accumulation acc = sum_k round(round(w_k - g) / K) in the precision of GDT
 // (worker-major order, EDT_LM/diloco.py:243-246). MODE_PARTIAL sums the rounded quotients
 // in fp32 instead (the cross-rank sum is then an fp32 RCCL reduction).
-template <int GDT, int WDT, int KC, int DIV, int MODE, int N, class A, int H2 = 4, bool BC = false>
+template <int GDT, int WDT, int KC, int DIV, int MODE, int N, class A, int H2 = 4, bool BC = false, bool SC = false>
 __device__ __forceinline__ void outer_elems(const A& a, uint64_t i) {
     float g[N], acc[N], b_in[N];
     ld<GDT, N, (EDT_NT_RMW != 0), H2>(a.theta, i, g);
@@ -89,6 +91,11 @@ __device__ __forceinline__ void outer_elems(const A& a, uint64_t i) {
         float grad[N];
 #pragma unroll
         for (int j = 0; j < N; ++j) grad[j] = -acc[j];               // p.grad = -avg_delta
+        if constexpr (SC) {                                          // clipped: one fp32 multiply, rounded
+#pragma unroll
+            for (int j = 0; j < N; ++j) grad[j] = grad[j] * a.grad_scale;
+            rnd<GDT>(grad);
+        }
         sgd_update<GDT, N, H2>(g, grad, a.mom, i, a.sgd, b_in);
         st<GDT, N, (EDT_NT_STORES != 0), H2>(a.theta, i, g);
         if constexpr (BC) {
@@ -104,7 +111,8 @@ __device__ __forceinline__ void outer_elems(const A& a, uint64_t i) {
 // DIV = 1: true division by K (torch CPU `delta / num_models`); DIV = 0: multiply by 1/K,
 // bit-identical when K is a power of two.
 // BC: also store round_w(theta_new) into a.bc (edt_outer_step_bcast).
-template <int GDT, int WDT, int KC, int DIV, int MODE, int N, bool BC = false>
+// SC: grad = round_g(-acc * a.grad_scale) (edt_outer_step_scaled).
+template <int GDT, int WDT, int KC, int DIV, int MODE, int N, bool BC = false, bool SC = false>
 __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_kernel(OuterArgs a) {
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     const uint64_t tid = xcd_block(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
@@ -113,17 +121,17 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_kernel(OuterArgs 
         constexpr int H2 = 4 * kBlock;
         const uint64_t nv = a.n / (kVec * kBlock) * kBlock;
         for (uint64_t v = tid; v < nv; v += stride)
-            outer_elems<GDT, WDT, KC, DIV, MODE, kVec, OuterArgs, H2, BC>(a, v * kVec - 4 * threadIdx.x);
+            outer_elems<GDT, WDT, KC, DIV, MODE, kVec, OuterArgs, H2, BC, SC>(a, v * kVec - 4 * threadIdx.x);
         for (uint64_t e = nv * kVec + tid; e < a.n; e += stride)     // scalar tail (< 8 x kBlock)
-            outer_elems<GDT, WDT, KC, DIV, MODE, 1, OuterArgs, 4, BC>(a, e);
+            outer_elems<GDT, WDT, KC, DIV, MODE, 1, OuterArgs, 4, BC, SC>(a, e);
     } else if constexpr (N == kVec) {
         const uint64_t nv = a.n / kVec;
         for (uint64_t v = tid; v < nv; v += stride)
-            outer_elems<GDT, WDT, KC, DIV, MODE, kVec, OuterArgs, 4, BC>(a, v * kVec);
+            outer_elems<GDT, WDT, KC, DIV, MODE, kVec, OuterArgs, 4, BC, SC>(a, v * kVec);
         const uint64_t t = nv * kVec + tid;      // scalar tail (< 8 elements)
-        if (t < a.n) outer_elems<GDT, WDT, KC, DIV, MODE, 1, OuterArgs, 4, BC>(a, t);
+        if (t < a.n) outer_elems<GDT, WDT, KC, DIV, MODE, 1, OuterArgs, 4, BC, SC>(a, t);
     } else {
-        for (uint64_t e = tid; e < a.n; e += stride) outer_elems<GDT, WDT, KC, DIV, MODE, 1, OuterArgs, 4, BC>(a, e);
+        for (uint64_t e = tid; e < a.n; e += stride) outer_elems<GDT, WDT, KC, DIV, MODE, 1, OuterArgs, 4, BC, SC>(a, e);
     }
 }
 
@@ -311,7 +319,7 @@ __global__ __launch_bounds__(kBlock) void broadcast_theta_kernel(const void* the
 // ---------------------------------------------------------------------------------------
 // launch helpers
 
-template <int MODE, bool BC = false>
+template <int MODE, bool BC = false, bool SC = false>
 int launch_outer(int gdt, int wdt, const OuterArgs& a, bool vec, hipStream_t s) {
     const unsigned g = grid_for(a.n, vec);
     const int kc = MODE == MODE_CHAIN ? 0 : a.K;        // chained launches always take the generic loop
@@ -319,7 +327,7 @@ int launch_outer(int gdt, int wdt, const OuterArgs& a, bool vec, hipStream_t s) 
         return with_kc_div<KC_FUSED>(kc, a.div_exact, [&](auto KC, auto DIV) {
             return with_bool(vec, [&](auto V) {
                 constexpr int N = decltype(V)::value ? kVec : 1;
-                outer_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value, decltype(DIV)::value, MODE, N, BC>
+                outer_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value, decltype(DIV)::value, MODE, N, BC, SC>
                     <<<g, kBlock, 0, s>>>(a);
                 return check_launch("outer_kernel");
             });
@@ -442,6 +450,23 @@ int edt_outer_step_tail(void* theta_g, int gdt, const void* const* theta_k, int 
     if (gdt == EDT_BF16) a.sgd.tail = tail_bits;    // fp32: torch's tails are FMAs too, nothing to emulate
     if (n == 0) return EDT_OK;
     return launch_outer<MODE_FUSED>(gdt, wdt, a, vec, (hipStream_t)stream);
+}
+
+int edt_outer_step_scaled(void* theta_g, int gdt, const void* const* theta_k, int wdt, int K,
+                          void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
+                          int nesterov, const uint8_t* tail_bits, float grad_scale, void* stream) {
+    g_err[0] = 0;
+    if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
+    if (!(grad_scale >= 0.f && grad_scale <= 1.f))          // NaN fails both comparisons
+        return fail(EDT_ERR_ARG, "grad_scale %g outside [0, 1]", (double)grad_scale);
+    OuterArgs a;
+    bool vec;
+    int rc = outer_prologue(a, vec, theta_g, gdt, theta_k, K, momentum, has_momentum, n, lr, momentum_coef, nesterov);
+    if (rc) return rc;
+    if (gdt == EDT_BF16) a.sgd.tail = tail_bits;
+    a.grad_scale = grad_scale;
+    if (n == 0) return EDT_OK;
+    return launch_outer<MODE_FUSED, false, true>(gdt, wdt, a, vec, (hipStream_t)stream);
 }
 
 int edt_outer_step_bcast(void* theta_g, int gdt, const void* const* theta_k, int wdt, int K,

@@ -1,0 +1,258 @@
+// edt_stats.hip — the pseudo-gradient statistics of the DiLoCo outer step (edt_delta_stats): one
+// read-only pass over theta and the K worker arenas that forms, per chunk of the arena, the fp64
+// sums of the very deltas and mean the fused step (edt_outer.hip) would apply to these operands,
+// and counts what is not finite — so a caller can screen workers and clip before theta is touched.
+// The per-element arithmetic is edt_step.h's (delta_of, mean_add: add_delta's two halves), the
+// sums' order edt_chunksum.h's (the canonical chunk-sum order).
+#include "edt_chunksum.h"
+#include "edt_step.h"
+
+namespace {
+
+// Workers per group: a lane holds the group's deltas of its 8 elements (64 floats) while their
+// sums are formed; with K <= kStatsGroup (one group) they are still there when the mean is known,
+// which is what the d_k . m sums need.
+constexpr int kStatsGroup = 8;
+constexpr int kStatsUpc = kTileSlots / kWavesPerBlock;        // units (workgroups) per chunk: 32
+constexpr int kStatsMaxWidth = 3 * EDT_MAX_WORKERS + 2;
+
+// Row of 3 K + 2 doubles: S_mm | S_kk[K] | S_km[K] | nonfinite_mean | nonfinite[K] (the counts are
+// small integers, exact in fp64 through every sum of the tree).
+__host__ __device__ constexpr int stats_width(int K) { return 3 * K + 2; }
+
+struct StatsWorkers {
+    const void* p[EDT_MAX_WORKERS];
+};
+
+struct StatsArgs {
+    const void* theta;
+    const uint64_t* chunks;
+    double* rows;
+    uint64_t units;      // nchunks * kStatsUpc
+    uint64_t u0;         // first unit of this launch
+    int K;
+    float kdiv;
+    float kinv;
+    StatsWorkers w;
+};
+
+template <int DT, bool VEC, bool NT>
+__device__ __forceinline__ void ld8(const void* p, uint64_t i, float (&x)[kVec]) {
+    if constexpr (VEC) {
+        ld<DT, kVec, NT>(p, i, x);
+    } else {                                          // an operand off a 16-byte boundary
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) {
+            float y[1];
+            ld<DT, 1>(p, i + j, y);
+            x[j] = y[0];
+        }
+    }
+}
+
+// Masks x in place: what is not finite becomes 0 (it adds nothing to a sum) and is counted.
+template <int N>
+__device__ __forceinline__ void mask_count(float (&x)[N], double& count) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const bool bad = (__float_as_uint(x[j]) & 0x7fffffffu) >= 0x7f800000u;
+        if (bad) {
+            x[j] = 0.f;
+            count += 1.0;
+        }
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void dot_chain(const float (&x)[N], const float (&y)[N], double& s) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) s = __builtin_fma((double)x[j], (double)y[j], s);
+}
+
+// One workgroup per unit of four tiles of a chunk, one tile per wave (for_tile's lane mapping; tile
+// 0's lanes also take the head / tail elements, after their vector). A lane without a vector or an
+// edge element computes on zeros: every delta is then +0, finite, and adds nothing. The four tile
+// sums are combined through LDS as the tree does, (t0 + t1) + (t2 + t3): a level-2 row per unit.
+// KM: K <= kStatsGroup, the S_km columns are formed; else they are written as 0.
+template <int GDT, int WDT, int DIV, int KC, bool KM, bool VEC>
+__global__ __launch_bounds__(kBlock) void delta_stats_kernel(StatsArgs a) {
+    __shared__ double part[kWavesPerBlock][kStatsMaxWidth];
+    const uint64_t u = a.u0 + blockIdx.x;
+    if (u >= a.units) return;                         // the whole workgroup
+    constexpr bool NT = nt_worker_loads<WDT, 4>();
+    constexpr int G = kStatsGroup;
+    const int K = KC > 0 ? KC : a.K;
+    const int wave = threadIdx.x >> 6;
+    const uint64_t c = u / kStatsUpc;
+    const int tile = (int)(u % kStatsUpc) * kWavesPerBlock + wave;
+    const uint64_t start = a.chunks[3 * c], len = a.chunks[3 * c + 1];
+    const uint64_t A = (start + kVec - 1) / kVec * kVec, B = (start + len) / kVec * kVec;
+    const uint64_t i = A + (uint64_t)tile * kTileElems + (uint64_t)(threadIdx.x & 63) * kVec;
+    const bool has_vec = A < B && i < B;
+    bool has_edge = false;
+    uint64_t e = 0;
+    if (tile == 0)
+        tile0_edge(start, len, [&](uint64_t x) {
+            has_edge = true;
+            e = x;
+        });
+
+    float g[kVec] = {}, ge[1] = {}, acc[kVec] = {}, acce[1] = {};
+    if (has_vec) ld8<GDT, VEC, false>(a.theta, i, g);
+    if (has_edge) ld<GDT, 1>(a.theta, e, ge);
+    double smm = 0.0, cm = 0.0, skm[G] = {};
+    double* row = &part[wave][0];
+
+    for (int k0 = 0; k0 < K; k0 += G) {               // KM: one group
+        float d[G][kVec], de[G][1];
+        double skk[G] = {}, ck[G] = {};
+#pragma unroll
+        for (int q = 0; q < G; ++q) {                 // the group's loads, issued together
+#pragma unroll
+            for (int j = 0; j < kVec; ++j) d[q][j] = 0.f;
+            de[q][0] = 0.f;
+            if (KC > 0 ? q < KC : k0 + q < K) {
+                if (has_vec) ld8<WDT, VEC, NT>(a.w.p[k0 + q], i, d[q]);
+                if (has_edge) ld<WDT, 1>(a.w.p[k0 + q], e, de[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < G; ++q) {
+            if (KC > 0 ? q < KC : k0 + q < K) {
+                delta_of<GDT>(d[q], g);
+                mean_add<GDT, DIV, true>(a, d[q], acc);
+                delta_of<GDT>(de[q], ge);
+                mean_add<GDT, DIV, true>(a, de[q], acce);
+                mask_count(d[q], ck[q]);
+                mask_count(de[q], ck[q]);
+                dot_chain(d[q], d[q], skk[q]);        // the lane's vector, then its edge element
+                dot_chain(de[q], de[q], skk[q]);
+            }
+        }
+        if constexpr (KM) {
+            mask_count(acc, cm);
+            mask_count(acce, cm);
+            dot_chain(acc, acc, smm);
+            dot_chain(acce, acce, smm);
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                dot_chain(d[q], acc, skm[q]);
+                dot_chain(de[q], acce, skm[q]);
+            }
+            double v[3 * G + 2], r[Red<3 * G + 2>::N2];
+            v[0] = smm;
+            v[2 * G + 1] = cm;
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                v[1 + q] = skk[q];
+                v[1 + G + q] = skm[q];
+                v[2 * G + 2 + q] = ck[q];
+            }
+            tile_reduce<3 * G + 2>(v, r);
+            red_store<3 * G + 2>(r, [&](int idx, double x) {
+                if (idx == 0) row[0] = x;
+                else if (idx <= G) { if (idx - 1 < K) row[idx] = x; }
+                else if (idx <= 2 * G) { if (idx - 1 - G < K) row[K + idx - G] = x; }
+                else if (idx == 2 * G + 1) row[2 * K + 1] = x;
+                else if (idx - 2 * G - 2 < K) row[2 * K + idx - 2 * G] = x;
+            });
+        } else {
+            double v[2 * G], r[Red<2 * G>::N2];
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                v[q] = skk[q];
+                v[G + q] = ck[q];
+            }
+            tile_reduce<2 * G>(v, r);
+            red_store<2 * G>(r, [&](int idx, double x) {
+                const int k = k0 + (idx < G ? idx : idx - G);
+                if (k < K) row[(idx < G ? 1 : 2 * K + 2) + k] = x;
+            });
+        }
+    }
+    if constexpr (!KM) {
+        mask_count(acc, cm);
+        mask_count(acce, cm);
+        dot_chain(acc, acc, smm);
+        dot_chain(acce, acce, smm);
+        const double v[2] = {smm, cm};
+        double r[Red<2>::N2];
+        tile_reduce<2>(v, r);
+        red_store<2>(r, [&](int idx, double x) { row[idx == 0 ? 0 : 2 * K + 1] = x; });
+    }
+    __syncthreads();
+    const int W = stats_width(K);
+    double* out = a.rows + unit_slot(u, a.units) * (uint64_t)W;
+    for (int q = threadIdx.x; q < W; q += kBlock) {
+        double x = 0.0;
+        if (KM || q <= K || q > 2 * K) x = (part[0][q] + part[1][q]) + (part[2][q] + part[3][q]);
+        out[q] = x;
+    }
+}
+
+template <int GDT, int WDT, int DIV, int KC, bool KM, bool VEC>
+int launch_stats(StatsArgs a, hipStream_t s) {
+    const uint64_t units = a.units;
+    for (uint64_t u0 = 0; u0 < units; u0 += kUnitGridCap) {
+        a.u0 = u0;
+        delta_stats_kernel<GDT, WDT, DIV, KC, KM, VEC><<<unit_grid(units - u0), kBlock, 0, s>>>(a);
+        if (int rc = check_launch("delta_stats_kernel")) return rc;
+    }
+    return EDT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t edt_delta_stats_doubles(int K, int64_t nchunks) {
+    if (K < 1 || K > EDT_MAX_WORKERS || nchunks < 0) return 0;
+    // the chunk rows, then one level-2 row per unit of four tiles
+    return (uint64_t)nchunks * (uint64_t)stats_width(K) * (1ull + kStatsUpc);
+}
+
+int edt_delta_stats(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K, uint64_t n,
+                    const uint64_t* chunk_desc, int64_t nchunks, double* out, void* stream) {
+    g_err[0] = 0;
+    if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
+    if (K < 1 || K > EDT_MAX_WORKERS)
+        return fail(EDT_ERR_ARG, "worker count %d out of range [1, %d]", K, EDT_MAX_WORKERS);
+    if (nchunks < 0) return fail(EDT_ERR_ARG, "negative chunk count");
+    if (!theta_k) return fail(EDT_ERR_ARG, "theta_k is null");
+    if (n == 0 || nchunks == 0) return EDT_OK;
+    if (!theta_g) return fail(EDT_ERR_ARG, "theta_g is null");
+    if (!chunk_desc || !out) return fail(EDT_ERR_ARG, "null chunk table or output");
+    if (reinterpret_cast<uintptr_t>(out) & 7u) return fail(EDT_ERR_ARG, "out must be 8-byte aligned");
+    StatsArgs a;
+    memset(&a, 0, sizeof(a));
+    bool vec = aligned16(theta_g);
+    for (int k = 0; k < K; ++k) {
+        if (!theta_k[k]) return fail(EDT_ERR_ARG, "theta_k[%d] is null", k);
+        a.w.p[k] = theta_k[k];
+        vec = vec && aligned16(theta_k[k]);
+    }
+    a.theta = theta_g;
+    a.chunks = chunk_desc;
+    a.rows = out + (uint64_t)nchunks * stats_width(K);
+    a.units = (uint64_t)nchunks * kStatsUpc;
+    a.K = K;
+    a.kdiv = (float)K;
+    a.kinv = 1.0f / (float)K;
+    hipStream_t s = (hipStream_t)stream;
+    const bool km = K <= kStatsGroup;
+    int rc = with_pair(gdt, wdt, [&](auto G, auto Wd) {
+        constexpr int GD = decltype(G)::value, WD = decltype(Wd)::value;
+        return with_bool(vec, [&](auto V) {
+            constexpr bool VEC = decltype(V)::value;
+            if (K == 8) return launch_stats<GD, WD, 0, 8, true, VEC>(a, s);
+            return with_bool(!is_pow2(K), [&](auto D) {
+                constexpr int DIV = decltype(D)::value ? 1 : 0;
+                return with_bool(km, [&](auto M) { return launch_stats<GD, WD, DIV, 0, decltype(M)::value, VEC>(a, s); });
+            });
+        });
+    });
+    if (rc) return rc;
+    return launch_tree_reduce(a.rows, stats_width(K), kStatsUpc, kStatsUpc, 1, nchunks, out, s);
+}
+
+}  // extern "C"

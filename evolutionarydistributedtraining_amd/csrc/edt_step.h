@@ -74,6 +74,34 @@ __device__ __forceinline__ void add_delta(const A& a, int k, const float (&g)[N]
     if constexpr (ROUND_ACC) rnd<GDT>(acc);
 }
 
+// add_delta's two halves on values already loaded, for the statistics pass (edt_stats.hip), which
+// sums the delta itself and the mean: delta_of is d_k = round(w_k - g) in place, mean_add the rest
+// of the chain (d is kept). add_delta keeps its own text: routing it through these two moved the
+// register allocation of the quantized partial kernels (the sensitivity noted above); the two
+// texts are held together by the test that the fused step's theta equals the statistics' mean.
+template <int GDT, int N>
+__device__ __forceinline__ void delta_of(float (&w)[N], const float (&g)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) w[j] = w[j] - g[j];
+    rnd<GDT>(w);
+}
+
+template <int GDT, int DIV, bool ROUND_ACC, int N, class A>
+__device__ __forceinline__ void mean_add(const A& a, const float (&d)[N], float (&acc)[N]) {
+    float w[N];
+    if constexpr (DIV) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = d[j] / a.kdiv;
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = d[j] * a.kinv;
+    }
+    rnd<GDT>(w);
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = acc[j] + w[j];
+    if constexpr (ROUND_ACC) rnd<GDT>(acc);
+}
+
 // a = ((p_0 + p_1) + ...) + p_{np-1} in fp32: the per-rank partials of one shard summed in rank
 // order (one fixed order whatever the collective library does). ld_rank(r, x) loads rank r's N
 // values: an fp32 ld, or ld_q of a packed region.

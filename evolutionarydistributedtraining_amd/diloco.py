@@ -56,6 +56,7 @@ class OuterState:
         # parameter tensors move, so no placement can hold.
         self.place_momentum = int(place_momentum)
         self.placement: dict | None = None
+        self.last_stats: dict | None = None         # the last guarded step's report (OuterGuard)
 
     def buffer_for(self, theta: torch.Tensor, numel: int | None = None) -> torch.Tensor:
         """The flat momentum for parameters like `theta` (numel: total count when theta is
@@ -108,6 +109,168 @@ class OuterState:
         return st
 
 
+class OuterGuard:
+    """Protection of theta and the outer momentum (opt-in, `guard=` of OuterSync, DirOuterSync and
+    outer_step): before the step, one read-only pass (`ops.delta_stats`) measures the
+    pseudo-gradient the step would apply — its norm, every worker's delta norm and cosine to the
+    mean, and what is not finite — and `guard_decision` screens the workers and clips.
+
+    max_grad_norm: clip the mean pseudo-gradient to this 2-norm (torch's clip_grad_norm_ formula
+    over the fp64 norm); None: no clipping.
+    on_nonfinite: "raise" (a NaN / Inf delta or mean raises NonFiniteWorkers, theta and the momentum
+    untouched), "drop" (the flagged workers are left out: a true mean over the survivors, measured
+    again) or "ignore" (report only).
+    min_workers: fewer workers (after a drop: survivors) than this raises.
+    per_tensor: last_stats also carries the figures per parameter tensor."""
+
+    POLICIES = ("raise", "drop", "ignore")
+
+    def __init__(self, max_grad_norm: float | None = None, on_nonfinite: str = "raise", min_workers: int = 1,
+                 per_tensor: bool = False):
+        if on_nonfinite not in self.POLICIES:
+            raise ValueError(f"on_nonfinite must be one of {self.POLICIES}, got {on_nonfinite!r}")
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm}")
+        if int(min_workers) < 1:
+            raise ValueError(f"min_workers must be at least 1, got {min_workers}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.on_nonfinite = on_nonfinite
+        self.min_workers = int(min_workers)
+        self.per_tensor = bool(per_tensor)
+
+
+class NonFiniteWorkers(EdtError):
+    """The guard refused the step. nonfinite[k]: worker k's count of non-finite delta elements;
+    nonfinite_mean: the mean's; survivors: the workers that were not flagged."""
+
+    def __init__(self, message: str, nonfinite, nonfinite_mean: int, survivors):
+        super().__init__(message)
+        self.nonfinite = [int(c) for c in nonfinite]
+        self.nonfinite_mean = int(nonfinite_mean)
+        self.survivors = list(survivors)
+
+
+def stats_totals(rows, K: int, first=None) -> dict:
+    """Totals of `ops.delta_stats` rows (host float64 [nchunks, 3 K + 2]) in float64, summed
+    sequentially in chunk order (cumsum, not numpy's pairwise sum, so the total is one fixed
+    function of the rows). first: per-segment first-chunk indices [nseg + 1] -> the same totals per
+    segment under "segments". S_km is None above 8 workers (the pass does not form it)."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 3 * K + 2)
+    cols = ops.stats_columns(K)
+
+    def total(r):
+        t = np.cumsum(r, axis=0)[-1] if len(r) else np.zeros(3 * K + 2)
+        return {"S_mm": float(t[0]), "S_kk": t[cols["S_kk"]].copy(),
+                "S_km": t[cols["S_km"]].copy() if K <= 8 else None,
+                "nonfinite_mean": int(t[2 * K + 1]), "nonfinite": t[cols["nonfinite"]].astype(np.int64)}
+
+    out = total(rows)
+    if first is not None:
+        out["segments"] = [total(rows[int(a):int(b)]) for a, b in zip(first[:-1], first[1:])]
+    return out
+
+
+def clip_coefficient(s_mm: float, max_grad_norm: float | None) -> float:
+    """min(1, max_norm / (norm + 1e-6)) over the fp64 norm sqrt(S_mm), evaluated in Python float64
+    and cast to float32 (what the kernel multiplies by): torch.nn.utils.clip_grad_norm_'s formula."""
+    import numpy as np
+    if max_grad_norm is None:
+        return 1.0
+    return float(np.float32(min(1.0, float(max_grad_norm) / (float(s_mm) ** 0.5 + 1e-6))))
+
+
+def guard_decision(totals: dict, guard: OuterGuard):
+    """(survivors, clip_coef) from the totals of one statistics pass: a pure function, no device.
+    survivors: indices of the workers the step averages. clip_coef: the float32 factor on the mean
+    pseudo-gradient (1.0: the plain step runs) — None when workers were dropped, since the norm of
+    what is applied is then that of a second pass over the survivors. Raises NonFiniteWorkers as
+    the policy says, and whenever fewer than min_workers would take part."""
+    nf = [int(c) for c in totals["nonfinite"]]
+    nfm = int(totals["nonfinite_mean"])
+    K = len(nf)
+    everyone = list(range(K))
+    flagged = [k for k in everyone if nf[k] > 0]
+    survivors = [k for k in everyone if nf[k] == 0]
+    if K < guard.min_workers:
+        raise NonFiniteWorkers(f"{K} workers, min_workers = {guard.min_workers}", nf, nfm, everyone)
+    if guard.on_nonfinite == "raise" and (flagged or nfm):
+        raise NonFiniteWorkers(f"non-finite pseudo-gradient: workers {flagged} (counts {nf}), mean {nfm}",
+                               nf, nfm, survivors)
+    if guard.on_nonfinite == "drop":
+        if len(survivors) < guard.min_workers:
+            raise NonFiniteWorkers(f"{len(survivors)} finite workers left of {K}, min_workers = "
+                                   f"{guard.min_workers} (counts {nf})", nf, nfm, survivors)
+        if flagged:
+            return survivors, None
+        if nfm:
+            raise NonFiniteWorkers(f"the mean of finite workers is not finite at {nfm} elements", nf, nfm, survivors)
+    return everyone, clip_coefficient(totals["S_mm"], guard.max_grad_norm)
+
+
+def _report(totals: dict) -> dict:
+    import numpy as np
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cos = None if totals["S_km"] is None else \
+            (totals["S_km"] / np.sqrt(totals["S_kk"] * totals["S_mm"])).tolist()
+    return {"grad_norm": float(totals["S_mm"]) ** 0.5, "worker_norms": np.sqrt(totals["S_kk"]).tolist(),
+            "cos_to_mean": cos, "nonfinite": [int(c) for c in totals["nonfinite"]],
+            "nonfinite_mean": int(totals["nonfinite_mean"])}
+
+
+def _stats_plan(state, theta: torch.Tensor, numels):
+    """The chunk plan of the statistics pass, kept on the state: one segment per tensor when the
+    sizes are given (per_tensor), else one over the arena."""
+    offs = [0]
+    for n in (numels if numels is not None else [theta.numel()]):
+        offs.append(offs[-1] + int(n))
+    if offs[-1] != theta.numel():
+        raise EdtError("the guard's per-tensor sizes do not add up to theta's size")
+    key = (tuple(offs), str(theta.device))
+    cached = getattr(state, "_stats_plan", None)
+    if cached is None or cached[0] != key:
+        cached = state._stats_plan = (key, ops.make_slerp_plan(offs, theta.device))
+    return cached[1]
+
+
+def _measure(theta, workers, plan, per_tensor: bool) -> dict:
+    rows = ops.delta_stats(theta, workers, plan).cpu().numpy()          # the step's one host sync
+    first = plan.seg_first.cpu().numpy() if per_tensor else None
+    return stats_totals(rows, len(workers), first)
+
+
+def _guard_pass(theta, workers, state, guard: OuterGuard, numels):
+    """Runs the statistics, decides, and records state.last_stats. Returns (survivor indices,
+    clip_coef). Raises before anything is written."""
+    K = len(workers)
+    if K > L_MAX:
+        raise EdtError(f"a guarded step takes at most {L_MAX} workers")
+    plan = _stats_plan(state, theta, numels if guard.per_tensor else None)
+    first = _measure(theta, workers, plan, guard.per_tensor)
+    rep = _report(first)
+    rep.update(clip_coef=None, dropped=[])
+    state.last_stats = rep
+    survivors, clip = guard_decision(first, guard)
+    final = first
+    if clip is None:                            # workers dropped: the norm of what is applied
+        final = _measure(theta, [workers[k] for k in survivors], plan, guard.per_tensor)
+        again = _report(final)
+        rep["dropped"] = [k for k in range(K) if k not in survivors]
+        rep["grad_norm"], rep["nonfinite_mean"] = again["grad_norm"], again["nonfinite_mean"]
+        if again["cos_to_mean"] is not None:
+            cos = [float("nan")] * K
+            for j, k in enumerate(survivors):
+                cos[k] = again["cos_to_mean"][j]
+            rep["cos_to_mean"] = cos
+        kept, clip = guard_decision(final, guard)
+        if clip is None:                        # cannot happen: every survivor was finite
+            raise EdtError("the survivors' statistics flagged a worker")
+    if guard.per_tensor:
+        rep["per_tensor"] = [_report(t) for t in final["segments"]]
+    rep["clip_coef"] = clip
+    return survivors, clip
+
+
 def _tail_bits(cpu_tails, numels, device, state=None, per_tensor=False):
     """cpu_tails = (vec_elems, num_threads) of the reference's host -> the device bitmask of its
     torch scalar-tail elements (torchcompat), or None. per_tensor: the tensor-list form's masks
@@ -133,8 +296,12 @@ def _tail_bits(cpu_tails, numels, device, state=None, per_tensor=False):
 
 def _step_flat(theta: torch.Tensor, workers: list[torch.Tensor], state: OuterState, lr: float,
                momentum: float, nesterov: bool, broadcast: list[torch.Tensor] | None = None,
-               tail_bits: torch.Tensor | None = None) -> None:
+               tail_bits: torch.Tensor | None = None, guard: OuterGuard | None = None, numels=None) -> None:
     check_sgd_hparams(lr, momentum, nesterov)
+    clip = 1.0
+    if guard is not None:                       # before anything is created or written
+        survivors, clip = _guard_pass(theta, workers, state, guard, numels)
+        workers = [workers[k] for k in survivors]
     state.hparams = dict(lr=lr, momentum=momentum, nesterov=nesterov)
     fresh = state.momentum is None
     mom = state.buffer_for(theta) if momentum != 0 else None
@@ -146,7 +313,11 @@ def _step_flat(theta: torch.Tensor, workers: list[torch.Tensor], state: OuterSta
         except EdtError as e:                   # e.g. operands the probe cannot stream (alignment)
             state.placement = {"candidates": 1, "probe_ms": [], "chosen": 0, "skipped": str(e)}
     has = state.has_momentum if momentum != 0 else False
-    if tail_bits is not None and broadcast:              # the tail form has no fused broadcast
+    if clip != 1.0:                                      # clipped: the scaled form has no fused broadcast
+        ops.outer_step_scaled(theta, workers, mom, has, lr, momentum, nesterov, clip, tail_bits=tail_bits)
+        if broadcast:
+            ops.broadcast_theta(theta, broadcast)
+    elif tail_bits is not None and broadcast:            # the tail form has no fused broadcast
         ops.outer_step(theta, workers, mom, has, lr, momentum, nesterov, tail_bits=tail_bits)
         for b in broadcast:
             b.copy_(theta)
@@ -179,7 +350,8 @@ def _step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]], st
 
 
 def outer_step(base_params, worker_params, state: OuterState | None = None, lr: float = 0.7,
-               momentum: float = 0.9, nesterov: bool = True, cpu_tails: tuple[int, int] | None = None) -> OuterState:
+               momentum: float = 0.9, nesterov: bool = True, cpu_tails: tuple[int, int] | None = None,
+               guard: OuterGuard | None = None) -> OuterState:
     """Drop-in for EDT_LM/diloco.py:238-289 on device-resident parameters.
 
     base_params:   list of the global model's parameters (`list(base_model.parameters())`),
@@ -193,6 +365,10 @@ def outer_step(base_params, worker_params, state: OuterState | None = None, lr: 
     bit-exact with the reference run there, torch's scalar tails included (torchcompat; r5: the
     tensor-list form reads per-tensor masks, edt_outer_step_list_tail, so nothing is packed; the
     masks are kept on `state` across generations).
+    guard: an OuterGuard — the pseudo-gradient is measured, screened and clipped before the step
+    (state.last_stats). The statistics pass reads flat arenas, so lists that are not arena views are
+    packed first (a copy of every operand, as populations above 64 workers already cost), and a
+    guarded step takes at most 64 workers.
     """
     state = state or OuterState()
     base_params = list(base_params)
@@ -206,7 +382,9 @@ def outer_step(base_params, worker_params, state: OuterState | None = None, lr: 
     with torch.no_grad():
         theta = flat_view(base_params)
         flats = [flat_view(w) for w in worker_params]
-        if theta is None or any(f is None for f in flats):
+        if guard is not None and len(worker_params) > L_MAX:
+            raise EdtError(f"a guarded step takes at most {L_MAX} workers")
+        if guard is None and (theta is None or any(f is None for f in flats)):
             bf16_master = base_params and base_params[0].dtype == torch.bfloat16
             if (cpu_tails is None or bf16_master) and len(worker_params) <= L_MAX and base_params \
                     and all(p.is_cuda for p in base_params):
@@ -224,7 +402,8 @@ def outer_step(base_params, worker_params, state: OuterState | None = None, lr: 
         if len(wdt) != 1:
             raise EdtError("all trained models must share one dtype")
         _step_flat(theta, flats, state, lr, momentum, nesterov,
-                   tail_bits=_tail_bits(cpu_tails, [p.numel() for p in base_params], theta.device, state))
+                   tail_bits=_tail_bits(cpu_tails, [p.numel() for p in base_params], theta.device, state),
+                   guard=guard, numels=[p.numel() for p in base_params])
         if copied:
             unpack_(theta, base_params)
     return state
@@ -239,7 +418,10 @@ class OuterSync:
 
     def __init__(self, theta: ParamArena, workers: list[ParamArena], lr: float = 0.7,
                  momentum: float = 0.9, nesterov: bool = True, state: OuterState | None = None,
-                 cpu_tails: tuple[int, int] | None = None):
+                 cpu_tails: tuple[int, int] | None = None, guard: OuterGuard | None = None):
+        if guard is not None and len(workers) > L_MAX:
+            raise EdtError(f"a guarded step takes at most {L_MAX} workers")
+        self.guard = guard
         self.theta = theta
         self.workers = workers
         self.lr, self.momentum, self.nesterov = lr, momentum, nesterov
@@ -251,10 +433,20 @@ class OuterSync:
     def step(self, broadcast: bool = False) -> None:
         """One outer step. broadcast=True also starts every worker from the new global weights
         (EDT_LM/diloco.py:302-308) in the same pass: each worker arena is overwritten with theta
-        rounded to its dtype right after the kernel has read it (edt_outer_step_bcast)."""
+        rounded to its dtype right after the kernel has read it (edt_outer_step_bcast).
+        With a guard (OuterGuard) the statistics pass runs first and decides: see last_stats. The
+        broadcast then still reaches every worker arena, a dropped one included, so it rejoins
+        from the new theta; after a clipped step it is a pass of its own (edt_broadcast_theta)."""
         ws = [w.flat for w in self.workers]
         _step_flat(self.theta.flat, ws, self.state, self.lr, self.momentum, self.nesterov,
-                   ws if broadcast else None, tail_bits=self.tail_bits)
+                   ws if broadcast else None, tail_bits=self.tail_bits, guard=self.guard,
+                   numels=self.theta.layout.numels)
+
+    @property
+    def last_stats(self) -> dict | None:
+        """The last guarded step's report: grad_norm, worker_norms, cos_to_mean (None above 8
+        workers), nonfinite, nonfinite_mean, clip_coef, dropped, and per_tensor when asked for."""
+        return self.state.last_stats
 
     def place_momentum(self, candidates: int = 8) -> dict:
         """Choose where the outer momentum lives in HBM by measurement, once, for the life of
@@ -335,14 +527,20 @@ class DirOuterSync:
     worker arenas, the momentum) in that many regions of HBM (placement.place_set). Off by default
     here: a generation through checkpoint files takes ~1 s, of which the step is 12 ms, and three
     draws cost 1.79 s once (profiles/r06_e2e_checkpoint_publish.jsonl) — OuterSync.place_arenas is
-    the resident kernel loop's form."""
+    the resident kernel loop's form.
+    guard: an OuterGuard. The step is measured, screened and clipped before theta is touched
+    (last_stats); when it raises, nothing is written to any directory. The new weights still go to
+    every out dir, a dropped worker's included, so it rejoins from the new theta."""
 
     INNER_STATE_FILES = ("optimizer.pt", "scheduler.pt")
 
     def __init__(self, device=None, theta_dtype=None, worker_dtype=None, names=None,
                  lr=0.7, momentum=0.9, nesterov=True, state: OuterState | None = None,
                  state_path: str | None = None, carry_inner_state: bool = False, place_momentum: int = 8,
-                 place_draws: int = 1):
+                 place_draws: int = 1, guard: OuterGuard | None = None):
+        if guard is not None and not isinstance(guard, OuterGuard):
+            raise TypeError("guard must be an OuterGuard")
+        self.guard = guard
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.theta_dtype, self.worker_dtype, self.names = theta_dtype, worker_dtype, names
         self.lr, self.momentum, self.nesterov = lr, momentum, nesterov
@@ -356,6 +554,10 @@ class DirOuterSync:
         self.place_candidates = place_momentum
         self.place_draws = place_draws
         self.placement = None             # the placement search's report, once it has run
+
+    @property
+    def last_stats(self) -> dict | None:
+        return self.state.last_stats
 
     def _layout_from(self, model_dir):
         from .checkpoint import checkpoint_files, read_header, _ST_DTYPES
@@ -395,7 +597,8 @@ class DirOuterSync:
             items.insert(0, (base_dir, self.theta.flat))
         read_many(items, self.layout, self.names)        # the K + 1 checkpoints read in parallel
         workers = [w.flat for w in self.workers[:len(worker_dirs)]]
-        _step_flat(self.theta.flat, workers, self.state, self.lr, self.momentum, self.nesterov)
+        _step_flat(self.theta.flat, workers, self.state, self.lr, self.momentum, self.nesterov,
+                   guard=self.guard, numels=self.layout.numels)
         if self.place_candidates > 1 and self.placement is None and self.momentum != 0 \
                 and self.theta.flat.device.type == "cuda":
             import time

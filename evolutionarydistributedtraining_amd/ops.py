@@ -80,6 +80,68 @@ def outer_step(theta: torch.Tensor, workers: list[torch.Tensor], momentum: torch
                                   L.ptr(ws), L.stream_ptr(theta.device)), "edt_outer_step_ws")
 
 
+def outer_step_scaled(theta: torch.Tensor, workers: list[torch.Tensor], momentum: torch.Tensor | None,
+                      has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool, grad_scale: float,
+                      tail_bits: torch.Tensor | None = None) -> None:
+    """`outer_step` with a clipped pseudo-gradient (edt_outer_step_scaled): grad = round((-acc) *
+    grad_scale), one fp32 multiply, then the unchanged SGD update. grad_scale: finite, in [0, 1];
+    1.0 gives outer_step's bits. At most 64 workers, no fused broadcast (broadcast_theta after it)."""
+    lib = L.lib()
+    if not workers:
+        raise L.EdtError("no workers")
+    L.require_device(theta, momentum, *workers)
+    n = theta.numel()
+    if any(w.numel() != n or w.dtype != workers[0].dtype for w in workers):
+        raise L.EdtError("every worker buffer must match theta's size and share one dtype")
+    if len(workers) > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"the scaled step takes at most {L.EDT_MAX_WORKERS} workers")
+    _check_momentum(momentum, theta)
+    if tail_bits is not None:
+        L.require_device(tail_bits)
+        if tail_bits.dtype != torch.uint8 or tail_bits.numel() * 8 < n:
+            raise L.EdtError("tail_bits: uint8 with one bit per element")
+    L.check(lib.edt_outer_step_scaled(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
+                                      L.dtype_code(workers[0]), len(workers), L.ptr(momentum),
+                                      int(has_momentum), n, float(lr), float(momentum_coef), int(nesterov),
+                                      L.ptr(tail_bits), float(grad_scale), L.stream_ptr(theta.device)),
+            "edt_outer_step_scaled")
+
+
+def stats_columns(K: int) -> dict:
+    """Where a `delta_stats` row of 3 K + 2 doubles keeps what: column slices by name."""
+    return {"S_mm": slice(0, 1), "S_kk": slice(1, K + 1), "S_km": slice(K + 1, 2 * K + 1),
+            "nonfinite_mean": slice(2 * K + 1, 2 * K + 2), "nonfinite": slice(2 * K + 2, 3 * K + 2)}
+
+
+def delta_stats(theta: torch.Tensor, workers: list[torch.Tensor], plan: "SlerpPlan") -> torch.Tensor:
+    """Per-chunk statistics of the pseudo-gradient `outer_step` would apply to these operands, read
+    only (edt_delta_stats): float64 [plan.nchunks, 3 K + 2] on the device (`stats_columns`), fp64
+    sums in the canonical chunk-sum order of the deltas d_k = round(w_k - theta) and of the step's
+    mean m; what is not finite is left out of the sums and counted. S_km is zero for K > 8.
+    plan: `make_slerp_plan(seg_offsets, device)` over the arena's segments (absolute chunk starts;
+    the last offset is theta's size). The result is a view of the pooled workspace (`_scratch`):
+    read it before the next call on this stream overwrites it."""
+    lib = L.lib()
+    if not workers:
+        raise L.EdtError("no workers")
+    L.require_device(theta, *workers)
+    n, K = theta.numel(), len(workers)
+    if any(w.numel() != n or w.dtype != workers[0].dtype for w in workers):
+        raise L.EdtError("every worker buffer must match theta's size and share one dtype")
+    if K > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"the statistics pass takes at most {L.EDT_MAX_WORKERS} workers")
+    if plan.relative or plan.seg_offsets[0] != 0 or plan.seg_offsets[-1] != n:
+        raise L.EdtError("the chunk plan must cover theta's elements with absolute starts")
+    if plan.chunks.device != theta.device:
+        raise L.EdtError("the chunk plan lives on another device")
+    W = 3 * K + 2
+    out = _scratch(theta.device, int(lib.edt_delta_stats_doubles(K, plan.nchunks)))
+    L.check(lib.edt_delta_stats(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers), L.dtype_code(workers[0]),
+                                K, n, L.ptr(plan.chunks), plan.nchunks, L.ptr(out), L.stream_ptr(theta.device)),
+            "edt_delta_stats")
+    return out[:plan.nchunks * W].view(plan.nchunks, W)
+
+
 def outer_step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]],
                     momenta: list[torch.Tensor] | None, has_momentum: bool, lr: float,
                     momentum_coef: float, nesterov: bool, tails=None) -> None:

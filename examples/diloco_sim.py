@@ -72,10 +72,15 @@ def inner_train(model, worker: int, gen: int, steps: int, device, lr: float = 3e
 
 
 def run(generations: int = 5, workers: int = 4, inner_steps: int = 20, device="cuda", seed: int = 0,
-        before_outer=None, after_outer=None, log=print):
+        before_outer=None, after_outer=None, log=print, max_grad_norm=None, on_nonfinite=None):
     """The simulation loop. before_outer(gen, base, replicas) / after_outer(gen, base, state) are
-    hooks (the tests snapshot and check the outer step there). Returns the eval losses."""
+    hooks (the tests snapshot and check the outer step there). Returns the eval losses.
+    max_grad_norm / on_nonfinite: run the outer step under a diloco.OuterGuard (off by default)
+    and log the pseudo-gradient's norm per outer step."""
     from evolutionarydistributedtraining_amd import diloco
+    guard = None
+    if max_grad_norm is not None or on_nonfinite is not None:
+        guard = diloco.OuterGuard(max_grad_norm=max_grad_norm, on_nonfinite=on_nonfinite or "raise")
     torch.manual_seed(seed)
     device = torch.device(device)
     base = TinyLM().to(device)
@@ -91,13 +96,18 @@ def run(generations: int = 5, workers: int = 4, inner_steps: int = 20, device="c
             before_outer(gen, base, replicas)
         with torch.no_grad():
             state = diloco.outer_step(list(base.parameters()), [list(m.parameters()) for m in replicas], state,
-                                      lr=0.7, momentum=0.9, nesterov=True)
+                                      lr=0.7, momentum=0.9, nesterov=True,
+                                      **({"guard": guard} if guard is not None else {}))
         if after_outer:
             after_outer(gen, base, state)
         with torch.no_grad():
             ev = float(loss_of(base, batch(999_999, device, 64)))
         evals.append(ev)
         log(f"generation {gen}: eval loss {ev:.4f}")
+        if guard is not None:
+            st = state.last_stats
+            log(f"generation {gen}: pseudo-gradient norm {st['grad_norm']:.6g}, clip {st['clip_coef']:.6g}, "
+                f"dropped {st['dropped']}")
     return evals
 
 
@@ -106,8 +116,12 @@ def main():
     ap.add_argument("--generations", type=int, default=5)
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--inner-steps", type=int, default=20)
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the outer pseudo-gradient to this 2-norm (diloco.OuterGuard)")
+    ap.add_argument("--on-nonfinite", choices=("raise", "drop", "ignore"), default=None,
+                    help="what a NaN / Inf worker does to the outer step (diloco.OuterGuard)")
     a = ap.parse_args()
-    run(a.generations, a.workers, a.inner_steps)
+    run(a.generations, a.workers, a.inner_steps, max_grad_norm=a.max_grad_norm, on_nonfinite=a.on_nonfinite)
 
 
 if __name__ == "__main__":

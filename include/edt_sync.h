@@ -97,6 +97,34 @@ int edt_pair_merge_tail(const void* b1, const void* b2, const void* m1, const vo
                         int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
                         const uint8_t* tail_bits, void* stream);
 
+/* Pseudo-gradient statistics of the step edt_outer_step would take on these operands, read-only
+ * (theta and the workers are not written). Per element i and worker k, in theta's dtype g:
+ *   d_k = round_g(f32(theta_k[i]) - f32(theta_g[i]))
+ *   m   = the step's mean pseudo-gradient: acc = 0; for k in order: acc = round_g(acc +
+ *         round_g(d_k / K))   (true division unless K is a power of two, as the step)
+ * chunk_desc (device): nchunks chunks {start, length, segment} in edt_slerp_make_chunks' format
+ * (length <= 65,536, never across a segment, every element below n). out (device, 8-byte aligned,
+ * edt_delta_stats_doubles(K, nchunks) doubles): first the chunk rows [nchunks][3 K + 2]
+ *   S_mm = sum m^2 | S_kk[K] = sum d_k^2 | S_km[K] = sum d_k m | nonfinite_mean | nonfinite[K]
+ * then the pass's row scratch. Every sum is fp64 in the canonical chunk-sum order of the SLERP
+ * passes (per-lane FMA chains in element order, the descending xor butterfly per tile, the binary
+ * tree over the 128 tile sums). An element whose d_k is not finite adds nothing to S_kk[k] and
+ * S_km[k] and is counted in nonfinite[k]; one whose m is not finite adds nothing to S_mm or any
+ * S_km and is counted in nonfinite_mean. The counts are whole numbers stored as doubles (at most
+ * 65,536 per chunk, exact). S_km is formed for K <= 8 and written as 0 above. Operands off a
+ * 16-byte boundary take scalar loads; the sums are the same. 1 <= K <= EDT_MAX_WORKERS. */
+uint64_t edt_delta_stats_doubles(int K, int64_t nchunks);
+int edt_delta_stats(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K, uint64_t n,
+                    const uint64_t* chunk_desc, int64_t nchunks, double* out, void* stream);
+
+/* edt_outer_step_tail with a clipped pseudo-gradient: grad = round_g((-acc) * grad_scale), one
+ * fp32 multiply rounded to theta's dtype, then the unchanged SGD update. grad_scale must be finite
+ * and in [0, 1] (EDT_ERR_ARG otherwise); 1.0f gives edt_outer_step_tail's bits. tail_bits may be
+ * NULL. No fused broadcast (edt_broadcast_theta after it) and K <= EDT_MAX_WORKERS only. */
+int edt_outer_step_scaled(void* theta_g, int gdt, const void* const* theta_k, int wdt, int K,
+                          void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
+                          int nesterov, const uint8_t* tail_bits, float grad_scale, void* stream);
+
 /* The same step for any population size: K > EDT_MAX_WORKERS runs as consecutive launches of
  * <= 64 workers (the reference's worker order), the running sum carried in `workspace` (n
  * elements of theta's dtype: lossless, the sum is rounded to that dtype after every add).
