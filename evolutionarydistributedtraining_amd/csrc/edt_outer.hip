@@ -613,7 +613,9 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     if (chunks == 0) return EDT_OK;
     if (chunks > 0x7fffffffull) return fail(EDT_ERR_ARG, "too many elements for one launch");
     hipStream_t st = (hipStream_t)stream;
-    // pageable source: the copy is staged before hipMemcpyAsync returns, stream-ordered on the device
+    // pageable source, overwritten by this thread's next call: the runtime has read it when
+    // hipMemcpyAsync returns and the copy is stream-ordered on the device — pinned by
+    // tests/test_gpu_list_step.py::test_back_to_back_steps (two tables of up to 4.5 MB, no host wait)
     hipError_t e = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "tensor table upload failed: %s", hipGetErrorString(e));
     const uint64_t* d = static_cast<const uint64_t*>(workspace);

@@ -140,8 +140,9 @@ def test_diloco_golden_tensor_list(golden, oracle, dev, ops, idx):
                                      (torch.bfloat16, torch.bfloat16)])
 @pytest.mark.parametrize("K", [1, 3, 5, 8, 32])
 def test_outer_step_list_vs_oracle(oracle, dev, ops, gdt, wdt, K):
-    """Ragged tensor lists: empty tensors, sizes around the 32768-element chunk and the 8-element
-    vector, a tensor off a 16-byte boundary (scalar body), separate allocations per worker."""
+    """Ragged tensor lists: empty tensors, multi-chunk sizes around 32768 (the kernel's chunk is
+    4096 elements; its chunk and tile edges are in tests/test_gpu_list_step.py) and around the
+    8-element vector, a tensor off a 16-byte boundary (scalar body), separate allocations per worker."""
     numels = [0, 1, 7, 8, 9, 32767, 32768, 32769, 100_003, 0, 65536 * 3 + 5, 13]
     n = sum(numels)
     theta, workers, mom = _rand_case(n, K, gdt, wdt, seed=K + 17)
