@@ -50,6 +50,10 @@ SIGNATURES = [
     ("edt_delta_partial", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _P, _I, _P]),
     ("edt_sgd_apply", _I, [_P, _I, _P, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_sgd_apply_sum", _I, [_P, _I, ctypes.POINTER(_P), _I, _P, _I, _U64, _D, _D, _I, _P]),
+    ("edt_sgd_apply_scaled", _I, [_P, _I, _P, _P, _I, _U64, _D, _D, _I, ctypes.c_float, _P]),
+    ("edt_sgd_apply_sum_scaled", _I, [_P, _I, ctypes.POINTER(_P), _I, _P, _I, _U64, _D, _D, _I, ctypes.c_float, _P]),
+    ("edt_partial_sum_stats_doubles", _U64, [ctypes.c_int64]),
+    ("edt_partial_sum_stats", _I, [ctypes.POINTER(_P), _I, _I, _U64, _P, ctypes.c_int64, _P, _P]),
     ("edt_q_region_bytes", _U64, [_U64, _I]),
     ("edt_delta_partial_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _U64, _I, _P, _P, _P]),
     ("edt_sgd_apply_sum_q", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P]),

@@ -234,25 +234,32 @@ struct Partials {
     const float* p[EDT_MAX_WORKERS];
 };
 
-template <int GDT, int N>
+// SC: grad = round_g((-sum) * grad_scale) (edt_sgd_apply_sum_scaled, edt_sgd_apply_scaled). The clip
+// coefficient is a trailing argument only the SC instantiations have (`scale` is one float with SC,
+// nothing without), so the unscaled kernels keep their argument block, hidden arguments included.
+template <int GDT, int N, bool SC = false, class... S>
 __global__ __launch_bounds__(kBlock) void sgd_apply_sum_kernel(void* theta, Partials P, int np, void* mom,
-                                                               uint64_t n, SgdScalars s) {
+                                                               uint64_t n, SgdScalars s, S... scale) {
+    static_assert(sizeof...(S) == (SC ? 1 : 0), "one grad_scale with SC, none without");
     for_vec_tail<N>(n, [&](auto tagN, uint64_t i) {
         constexpr int M = decltype(tagN)::value;
         float g0[M], g[M];
-        sgd_from_sum<GDT, M>(theta, mom, i, s, np, [&](int r, float (&x)[M]) { ld<EDT_F32, M>(P.p[r], i, x); }, g0, g);
+        sgd_from_sum<GDT, M, SC>(theta, mom, i, s, np, [&](int r, float (&x)[M]) { ld<EDT_F32, M>(P.p[r], i, x); }, g0, g,
+                                 scale...);
         st<GDT, M>(theta, i, g);
     });
 }
 
 // SGD from a reduced fp32 sum (the "reduce" schedule): the same step from one partial.
-template <int GDT, int N>
+template <int GDT, int N, bool SC = false, class... S>
 __global__ __launch_bounds__(kBlock) void sgd_apply_kernel(void* theta, const float* acc, void* mom,
-                                                           uint64_t n, SgdScalars s) {
+                                                           uint64_t n, SgdScalars s, S... scale) {
+    static_assert(sizeof...(S) == (SC ? 1 : 0), "one grad_scale with SC, none without");
     for_vec_tail<N>(n, [&](auto tagN, uint64_t i) {
         constexpr int M = decltype(tagN)::value;
         float g0[M], g[M];
-        sgd_from_sum<GDT, M>(theta, mom, i, s, 1, [&](int, float (&x)[M]) { ld<EDT_F32, M>(acc, i, x); }, g0, g);
+        sgd_from_sum<GDT, M, SC>(theta, mom, i, s, 1, [&](int, float (&x)[M]) { ld<EDT_F32, M>(acc, i, x); }, g0, g,
+                                 scale...);
         st<GDT, M>(theta, i, g);
     });
 }
@@ -637,6 +644,65 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     return launch_list(gdt, wdt, L, !is_pow2(K), grid, st);
 }
 
+// The two sharded SGD entries and their scaled forms (SC: the clip coefficient is checked first,
+// so a refused call writes nothing).
+template <bool SC>
+static int sgd_apply_sum_impl(void* theta_g, int gdt, const float* const* acc_f32, int nacc, void* momentum,
+                              int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                              float grad_scale, void* stream) {
+    g_err[0] = 0;
+    int rc = check_master_dtype(gdt);
+    if (!rc) rc = check_partial_count(nacc);
+    if (!rc && SC) rc = check_grad_scale(grad_scale);
+    if (rc) return rc;
+    if (n == 0) return EDT_OK;
+    if (!theta_g || !acc_f32) return fail(EDT_ERR_ARG, "null buffer");
+    SgdScalars s;
+    if ((rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum))) return rc;
+    Partials P;
+    memset(&P, 0, sizeof(P));
+    bool vec = aligned16(theta_g) && (!s.use_momentum || aligned16(momentum));
+    if ((rc = fill_table(P.p, acc_f32, nacc, "acc_f32", vec))) return rc;
+    const unsigned g = grid_for(n, vec);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(gdt, [&](auto G) {
+        return with_bool(vec, [&](auto V) {
+            constexpr int GD = decltype(G)::value, N = decltype(V)::value ? kVec : 1;
+            if constexpr (SC)
+                sgd_apply_sum_kernel<GD, N, true><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s, grad_scale);
+            else
+                sgd_apply_sum_kernel<GD, N><<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+            return check_launch("sgd_apply_sum_kernel");
+        });
+    });
+}
+
+template <bool SC>
+static int sgd_apply_impl(void* theta_g, int gdt, const float* acc_f32, void* momentum, int has_momentum, uint64_t n,
+                          double lr, double momentum_coef, int nesterov, float grad_scale, void* stream) {
+    g_err[0] = 0;
+    int rc = check_master_dtype(gdt);
+    if (!rc && SC) rc = check_grad_scale(grad_scale);
+    if (rc) return rc;
+    if (n == 0) return EDT_OK;
+    if (!theta_g || !acc_f32) return fail(EDT_ERR_ARG, "null buffer");
+    SgdScalars s;
+    if ((rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum))) return rc;
+    const bool vec = aligned16(theta_g) && aligned16(acc_f32) && (!s.use_momentum || aligned16(momentum));
+    const unsigned g = grid_for(n, vec);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(gdt, [&](auto G) {
+        return with_bool(vec, [&](auto V) {
+            constexpr int GD = decltype(G)::value, N = decltype(V)::value ? kVec : 1;
+            if constexpr (SC)
+                sgd_apply_kernel<GD, N, true><<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s, grad_scale);
+            else
+                sgd_apply_kernel<GD, N><<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s);
+            return check_launch("sgd_apply_kernel");
+        });
+    });
+}
+
 extern "C" {
 
 int edt_outer_step_list(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
@@ -675,49 +741,27 @@ int edt_delta_partial(const void* theta_g, int gdt, const void* const* theta_k, 
 
 int edt_sgd_apply_sum(void* theta_g, int gdt, const float* const* acc_f32, int nacc, void* momentum,
                       int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
-    g_err[0] = 0;
-    int rc = check_master_dtype(gdt);
-    if (!rc) rc = check_partial_count(nacc);
-    if (rc) return rc;
-    if (n == 0) return EDT_OK;
-    if (!theta_g || !acc_f32) return fail(EDT_ERR_ARG, "null buffer");
-    SgdScalars s;
-    if ((rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum))) return rc;
-    Partials P;
-    memset(&P, 0, sizeof(P));
-    bool vec = aligned16(theta_g) && (!s.use_momentum || aligned16(momentum));
-    if ((rc = fill_table(P.p, acc_f32, nacc, "acc_f32", vec))) return rc;
-    const unsigned g = grid_for(n, vec);
-    hipStream_t st = (hipStream_t)stream;
-    return with_dtype(gdt, [&](auto G) {
-        return with_bool(vec, [&](auto V) {
-            sgd_apply_sum_kernel<decltype(G)::value, decltype(V)::value ? kVec : 1>
-                <<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
-            return check_launch("sgd_apply_sum_kernel");
-        });
-    });
+    return sgd_apply_sum_impl<false>(theta_g, gdt, acc_f32, nacc, momentum, has_momentum, n, lr, momentum_coef, nesterov,
+                                     1.f, stream);
+}
+
+int edt_sgd_apply_sum_scaled(void* theta_g, int gdt, const float* const* acc_f32, int nacc, void* momentum,
+                             int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                             float grad_scale, void* stream) {
+    return sgd_apply_sum_impl<true>(theta_g, gdt, acc_f32, nacc, momentum, has_momentum, n, lr, momentum_coef, nesterov,
+                                    grad_scale, stream);
 }
 
 int edt_sgd_apply(void* theta_g, int gdt, const float* acc_f32, void* momentum, int has_momentum,
                   uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
-    g_err[0] = 0;
-    int rc = check_master_dtype(gdt);
-    if (rc) return rc;
-    if (n == 0) return EDT_OK;
-    if (!theta_g || !acc_f32) return fail(EDT_ERR_ARG, "null buffer");
-    SgdScalars s;
-    if ((rc = shard_sgd(s, gdt, lr, momentum_coef, has_momentum, nesterov, momentum))) return rc;
-    const bool vec = aligned16(theta_g) && aligned16(acc_f32) && (!s.use_momentum || aligned16(momentum));
-    const unsigned g = grid_for(n, vec);
-    hipStream_t st = (hipStream_t)stream;
-    return with_dtype(gdt, [&](auto G) {
-        return with_bool(vec, [&](auto V) {
-            sgd_apply_kernel<decltype(G)::value, decltype(V)::value ? kVec : 1>
-                <<<g, kBlock, 0, st>>>(theta_g, acc_f32, momentum, n, s);
-            return check_launch("sgd_apply_kernel");
-        });
-    });
+    return sgd_apply_impl<false>(theta_g, gdt, acc_f32, momentum, has_momentum, n, lr, momentum_coef, nesterov, 1.f,
+                                 stream);
 }
 
+int edt_sgd_apply_scaled(void* theta_g, int gdt, const float* acc_f32, void* momentum, int has_momentum,
+                         uint64_t n, double lr, double momentum_coef, int nesterov, float grad_scale, void* stream) {
+    return sgd_apply_impl<true>(theta_g, gdt, acc_f32, momentum, has_momentum, n, lr, momentum_coef, nesterov,
+                                grad_scale, stream);
+}
 
 }  // extern "C"

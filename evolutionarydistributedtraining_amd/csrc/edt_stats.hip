@@ -201,9 +201,136 @@ int launch_stats(StatsArgs a, hipStream_t s) {
     return EDT_OK;
 }
 
+// ---- the mean pseudo-gradient of a sharded step, from the per-rank partials its owner holds ------
+// edt_partial_sum_stats: m = round_g(rank_sum of the shard's partials), exactly the value
+// sgd_from_sum negates into the gradient (edt_step.h: the same rank_sum, the same rnd), so a shard
+// owner can measure the step before theta is touched. delta_stats_kernel's unit, tile and lane
+// mapping and its (t0 + t1) + (t2 + t3) level-2 row, with a row of two: S_mm | nonfinite_mean.
+constexpr int kPartialStatsWidth = 2;
+
+struct StatsPartials {
+    const float* p[EDT_MAX_WORKERS];
+};
+
+struct PartialStatsArgs {
+    const uint64_t* chunks;
+    double* rows;
+    uint64_t units;
+    uint64_t u0;
+    int np;
+    StatsPartials P;
+};
+
+// NPC > 0: the partial count at compile time (rank_sum's loop unrolls and its loads issue
+// together); 0: the generic loop over a.np.
+template <int GDT, int NPC, bool VEC>
+__global__ __launch_bounds__(kBlock) void partial_sum_stats_kernel(PartialStatsArgs a) {
+    __shared__ double part[kWavesPerBlock][kPartialStatsWidth];
+    const uint64_t u = a.u0 + blockIdx.x;
+    if (u >= a.units) return;                         // the whole workgroup
+    const int np = NPC > 0 ? NPC : a.np;
+    const int wave = threadIdx.x >> 6;
+    const uint64_t c = u / kStatsUpc;
+    const int tile = (int)(u % kStatsUpc) * kWavesPerBlock + wave;
+    const uint64_t start = a.chunks[3 * c], len = a.chunks[3 * c + 1];
+    const uint64_t A = (start + kVec - 1) / kVec * kVec, B = (start + len) / kVec * kVec;
+    const uint64_t i = A + (uint64_t)tile * kTileElems + (uint64_t)(threadIdx.x & 63) * kVec;
+    const bool has_vec = A < B && i < B;
+    bool has_edge = false;
+    uint64_t e = 0;
+    if (tile == 0)
+        tile0_edge(start, len, [&](uint64_t x) {
+            has_edge = true;
+            e = x;
+        });
+
+    // a lane without a vector or an edge element sums zeros: m = +0, finite, adds nothing
+    float m[kVec], me[1];
+    rank_sum(np, m, [&](int r, float (&x)[kVec]) {
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) x[j] = 0.f;
+        if (has_vec) ld8<EDT_F32, VEC, false>(a.P.p[r], i, x);
+    });
+    rank_sum(np, me, [&](int r, float (&x)[1]) {
+        x[0] = 0.f;
+        if (has_edge) ld<EDT_F32, 1>(a.P.p[r], e, x);
+    });
+    rnd<GDT>(m);
+    rnd<GDT>(me);
+    double smm = 0.0, cm = 0.0;
+    mask_count(m, cm);
+    mask_count(me, cm);
+    dot_chain(m, m, smm);                             // the lane's vector, then its edge element
+    dot_chain(me, me, smm);
+    const double v[2] = {smm, cm};
+    double r[Red<2>::N2];
+    tile_reduce<2>(v, r);
+    red_store<2>(r, [&](int idx, double x) { part[wave][idx] = x; });
+    __syncthreads();
+    double* out = a.rows + unit_slot(u, a.units) * (uint64_t)kPartialStatsWidth;
+    if (threadIdx.x < kPartialStatsWidth) {
+        const int q = threadIdx.x;
+        out[q] = (part[0][q] + part[1][q]) + (part[2][q] + part[3][q]);
+    }
+}
+
+template <int GDT, int NPC, bool VEC>
+int launch_partial_stats(PartialStatsArgs a, hipStream_t s) {
+    const uint64_t units = a.units;
+    for (uint64_t u0 = 0; u0 < units; u0 += kUnitGridCap) {
+        a.u0 = u0;
+        partial_sum_stats_kernel<GDT, NPC, VEC><<<unit_grid(units - u0), kBlock, 0, s>>>(a);
+        if (int rc = check_launch("partial_sum_stats_kernel")) return rc;
+    }
+    return EDT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+uint64_t edt_partial_sum_stats_doubles(int64_t nchunks) {
+    if (nchunks < 0) return 0;
+    // the chunk rows, then one level-2 row per unit of four tiles
+    return (uint64_t)nchunks * (uint64_t)kPartialStatsWidth * (1ull + kStatsUpc);
+}
+
+int edt_partial_sum_stats(const float* const* acc_f32, int nacc, int gdt, uint64_t n, const uint64_t* chunk_desc,
+                          int64_t nchunks, double* out, void* stream) {
+    g_err[0] = 0;
+    int rc = check_master_dtype(gdt);
+    if (!rc) rc = check_partial_count(nacc);
+    if (rc) return rc;
+    if (nchunks < 0) return fail(EDT_ERR_ARG, "negative chunk count");
+    if (!acc_f32) return fail(EDT_ERR_ARG, "acc_f32 is null");
+    if (n == 0 || nchunks == 0) return EDT_OK;
+    if (!chunk_desc || !out) return fail(EDT_ERR_ARG, "null chunk table or output");
+    if (reinterpret_cast<uintptr_t>(out) & 7u) return fail(EDT_ERR_ARG, "out must be 8-byte aligned");
+    PartialStatsArgs a;
+    memset(&a, 0, sizeof(a));
+    bool vec = true;
+    if ((rc = fill_table(a.P.p, acc_f32, nacc, "acc_f32", vec))) return rc;
+    a.chunks = chunk_desc;
+    a.rows = out + (uint64_t)nchunks * kPartialStatsWidth;
+    a.units = (uint64_t)nchunks * kStatsUpc;
+    a.np = nacc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = with_dtype(gdt, [&](auto G) {
+        constexpr int GD = decltype(G)::value;
+        return with_bool(vec, [&](auto V) {
+            constexpr bool VEC = decltype(V)::value;
+            switch (nacc) {
+                case 1: return launch_partial_stats<GD, 1, VEC>(a, s);
+                case 2: return launch_partial_stats<GD, 2, VEC>(a, s);
+                case 4: return launch_partial_stats<GD, 4, VEC>(a, s);
+                case 8: return launch_partial_stats<GD, 8, VEC>(a, s);
+                default: return launch_partial_stats<GD, 0, VEC>(a, s);
+            }
+        });
+    });
+    if (rc) return rc;
+    return launch_tree_reduce(a.rows, kPartialStatsWidth, kStatsUpc, kStatsUpc, 1, nchunks, out, s);
+}
 
 uint64_t edt_delta_stats_doubles(int K, int64_t nchunks) {
     if (K < 1 || K > EDT_MAX_WORKERS || nchunks < 0) return 0;

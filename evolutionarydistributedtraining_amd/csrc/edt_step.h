@@ -118,10 +118,11 @@ __device__ __forceinline__ void rank_sum(int np, float (&a)[N], LD&& ld_rank) {
 
 // The sharded step's phase 2 for the N elements at i: grad = -round_g(rank_sum), then torch's SGD
 // step. g0 = theta as loaded, g = theta after the step (in registers: the caller stores g, or the
-// update g - g0); the momentum is updated in place.
-template <int GDT, int N, class LD>
+// update g - g0); the momentum is updated in place. SC: grad = round_g((-a) * grad_scale), the clipped
+// form (outer_elems' SC branch: one fp32 multiply, rounded); without it grad_scale is not read.
+template <int GDT, int N, bool SC = false, class LD>
 __device__ __forceinline__ void sgd_from_sum(const void* theta, void* mom, uint64_t i, const SgdScalars& s, int np,
-                                             LD&& ld_rank, float (&g0)[N], float (&g)[N]) {
+                                             LD&& ld_rank, float (&g0)[N], float (&g)[N], float grad_scale = 1.f) {
     float a[N], grad[N], b_in[N];
     ld<GDT, N>(theta, i, g0);
     ld_momentum<GDT, N>(mom, i, s, b_in);
@@ -129,6 +130,11 @@ __device__ __forceinline__ void sgd_from_sum(const void* theta, void* mom, uint6
     rnd<GDT>(a);
 #pragma unroll
     for (int j = 0; j < N; ++j) { grad[j] = -a[j]; g[j] = g0[j]; }   // p.grad = -avg_delta
+    if constexpr (SC) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) grad[j] = grad[j] * grad_scale;
+        rnd<GDT>(grad);
+    }
     sgd_update<GDT, N>(g, grad, mom, i, s, b_in);
 }
 
@@ -202,6 +208,13 @@ inline int check_master_dtype(int gdt) {
 inline int check_partial_count(int nacc) {
     if (nacc < 1 || nacc > EDT_MAX_WORKERS)
         return fail(EDT_ERR_ARG, "partial count %d out of range [1, %d]", nacc, EDT_MAX_WORKERS);
+    return EDT_OK;
+}
+
+// the clip coefficient of the scaled entries: finite, in [0, 1] (NaN fails both comparisons)
+inline int check_grad_scale(float grad_scale) {
+    if (!(grad_scale >= 0.f && grad_scale <= 1.f))
+        return fail(EDT_ERR_ARG, "grad_scale %g outside [0, 1]", (double)grad_scale);
     return EDT_OK;
 }
 

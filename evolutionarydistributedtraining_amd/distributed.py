@@ -66,6 +66,16 @@ on the comm stream overlaps the HBM-bound kernels on the compute stream:
                          With broadcast="workers" the step already does it and the flag changes
                          nothing. NaN elements (a scale-255 block) are NaN in theta and in every
                          worker; their payload bits are not specified.
+  guard=OuterGuard       (reduce, reduce_ordered, exact; opt-in) measures, screens and clips the step
+                         across the ranks before theta is touched: every rank forms the
+                         same float64 totals in one fixed order (its buckets and chunks in order, then
+                         the ranks in rank order after an all_gather_object) and takes the same
+                         diloco.guard_decision. The reduce schedules screen the local workers before
+                         the exchange (edt_delta_stats: S_kk and the non-finite counts) and measure
+                         the mean on the owned shards after it (edt_partial_sum_stats), clipping with
+                         edt_sgd_apply(_sum)_scaled; exact runs edt_delta_stats on the received slices
+                         and clips with edt_outer_step_scaled. A refusal leaves theta, the momentum and
+                         the worker arenas as they were on every rank, with every collective waited for.
   mode="auto" / broadcast="auto" (defaults) pick the combination with the fewest wire bytes,
   ties to exact, then reduce_ordered: at K = 8 bf16 workers, fp32 theta: N = 2 reduce_ordered/theta
   (8 B/elem), N = 4 and 8 exact/workers (6 and 4 B/elem); all fp32: N = 2 and 4 reduce_ordered,
@@ -101,8 +111,10 @@ class ShardedOuterSync:
                  broadcast: str = "auto", comm: Collectives | None = None,
                  cpu_tails: tuple[int, int] | None = None, wire_format: str = "mxfp8",
                  error_feedback: bool = True, gather_format: str | None = None, rounding: str = "nearest",
-                 seed: int = 0):
-        """mode="reduce_q": `wire_format` picks the element format of the quantized partials and
+                 seed: int = 0, guard=None):
+        """guard: a diloco.OuterGuard — every step is measured, screened and clipped across the ranks
+        before theta is touched (`_guarded`, `last_stats`); None: nothing changes.
+        mode="reduce_q": `wire_format` picks the element format of the quantized partials and
         `error_feedback` keeps `self.residual` — this rank's fp32 quantization error (n_pad
         elements), added to the next step's partial before it is quantized. The residual is per
         rank (each rank quantizes its own partial) and is not part of theta or the momentum: a
@@ -163,6 +175,14 @@ class ShardedOuterSync:
         self.k_total = k_local * self.world
         self.rounding, self.seed = rounding, int(seed)
         self.q_step = 0                # stochastic rounding: the step counter of the random bits
+        self.guard = guard
+        self.last_stats = None         # the last guarded step's report, identical on every rank
+        # what a guarded step hands its phases (reset after every step): the local survivors and
+        # divisor of phase 1, the surviving global workers of the exact step, the clip coefficient
+        self._phase1, self._exact_idx, self._clip = None, None, 1.0
+        self._guard_plans = {}
+        if guard is not None:
+            self._check_guard()
         n = layout.total
         # buckets: multiples of world * 64 elements so every shard is 16-byte aligned (reduce_q:
         # world * 512, so every shard is a whole region of the wire format)
@@ -233,9 +253,52 @@ class ShardedOuterSync:
             return fn(*args, **kw)
         a, b = self.event_factory(), self.event_factory()
         a.record()
-        fn(*args, **kw)
+        got = fn(*args, **kw)
         b.record()
         self.kernel_events.append((a, b))
+        return got
+
+    def _check_guard(self):
+        """The constructor's refusals of guard=: each says what is missing."""
+        from .diloco import OuterGuard
+        if not isinstance(self.guard, OuterGuard):
+            raise TypeError("guard must be an OuterGuard")
+        if self.mode == "reduce_q":
+            raise ValueError("guard= does not take mode='reduce_q': a dropped worker or a refused step would have "
+                             "to take back what phase 1 already folded into the error-feedback residuals (and the "
+                             "stochastic q_step), which that schedule does not define yet (DESIGN §9)")
+        if self.guard.per_tensor:
+            raise ValueError("guard.per_tensor is not available on the sharded step: shards cut tensors, so no "
+                             "rank holds a tensor's rows")
+        if self.k_total > 64:
+            raise EdtError(f"a guarded step takes at most 64 workers in all, not {self.k_total}")
+        k = self.kernels
+        if self.mode == "exact":
+            need = ["make_slerp_plan", "delta_stats", "outer_step_scaled"]
+        else:
+            need = ["make_slerp_plan", "delta_stats", "partial_sum_stats", "sgd_apply_scaled"]
+            if self.mode == "reduce_ordered" and hasattr(k, "sgd_apply_sum"):
+                need[-1] = "sgd_apply_sum_scaled"
+        missing = [m for m in need if not hasattr(k, m)]
+        if missing:
+            raise EdtError(f"guard= with mode={self.mode!r} needs kernels that provide {need}; "
+                           f"{type(k).__name__ if not hasattr(k, '__name__') else k.__name__} lacks {missing}")
+
+    def guard_bytes(self) -> int:
+        """Algorithmic HBM bytes the guard adds to one step on this rank (no drop; kernel_bytes()
+        keeps its meaning). Reduce schedules: edt_delta_stats over the local arenas (theta and the
+        K_local workers, whole arena) and edt_partial_sum_stats over the owned shards' partials (N
+        of them, reduce: the one reduced shard); exact: edt_delta_stats over the owned shards with
+        all K received slices. 0 without a guard."""
+        if self.guard is None:
+            return 0
+        wb = self.worker_bufs[0].element_size()
+        gb = self.theta_buf.element_size()
+        shard = self.n_pad // self.world
+        if self.mode == "exact":
+            return shard * (self.k_total * wb + gb)
+        nacc = self.world if self.mode == "reduce_ordered" else 1
+        return self.n_pad * (self.k_local * wb + gb) + shard * 4 * nacc
 
     def kernel_bytes(self, broadcast: bool = False) -> int:
         """Algorithmic HBM bytes of one step's local kernels on this rank (steady state:
@@ -309,17 +372,20 @@ class ShardedOuterSync:
         refresh = broadcast and self.broadcast != "workers"
         produce = getattr(self, "_produce_" + self.mode)
         consume = getattr(self, "_consume_" + self.mode)
-        works = [produce(b, e) for b, e in self.buckets]
-        gathers = []
-        mom_off = 0
-        for (b, e), ws in zip(self.buckets, works):
-            for w in ws:
-                w.wait()
-            s0, s1 = self._shard(b, e)
-            sl = slice(mom_off, mom_off + (s1 - s0))
-            mom = None if self.mom_shard is None else self.mom_shard[sl]
-            gathers.append(consume(b, e, s0, s1, mom, sl))
-            mom_off = sl.stop
+        if self.guard is not None:
+            # measured, screened and clipped first (_guarded): every exchange is waited for before
+            # the decision, so nothing below runs on a step the guard refuses
+            try:
+                gathers = self._guarded(produce, consume)
+            finally:
+                self._phase1, self._exact_idx, self._clip = None, None, 1.0
+        else:
+            works = [produce(b, e) for b, e in self.buckets]
+            gathers = []
+            for (b, e, s0, s1, mom, sl), ws in zip(self._owned(), works):
+                for w in ws:
+                    w.wait()
+                gathers.append(consume(b, e, s0, s1, mom, sl))
         if self.mode == "reduce_q" and self.gather_format is not None:
             # phase 3: as each bucket's updates land, every rank adds the same D(q) to its replica
             gf = self.gather_format
@@ -343,6 +409,134 @@ class ShardedOuterSync:
         if self.momentum:
             self.has_momentum = True
 
+    def _owned(self):
+        """Per bucket (b, e), the owned shard [s0, s1) and its slice `sl` of the sharded momentum
+        (`mom`, or None)."""
+        mom_off = 0
+        for b, e in self.buckets:
+            s0, s1 = self._shard(b, e)
+            sl = slice(mom_off, mom_off + (s1 - s0))
+            yield b, e, s0, s1, (None if self.mom_shard is None else self.mom_shard[sl]), sl
+            mom_off = sl.stop
+
+    # ---- the guarded step (guard=OuterGuard) -----------------------------------------------
+    # One rule: every rank forms the same float64 totals from the same numbers in the same order —
+    # per rank its buckets in order and their chunks in order (cumsum), then the ranks in rank order
+    # after an all_gather_object of the per-rank totals, never an all-reduce in the library's own
+    # order — and calls the same pure diloco.guard_decision on them. So every rank steps, or every
+    # rank raises the same exception, with every issued collective waited for.
+
+    def _stats_plan(self, n):
+        plan = self._guard_plans.get(n)
+        if plan is None:
+            plan = self._guard_plans[n] = self.kernels.make_slerp_plan([0, n], self.theta_buf.device)
+        return plan
+
+    def _rank_totals(self, rows: list, width: int):
+        """rows: this rank's per-bucket row blocks (device, consumed before the next statistics
+        call reuses the workspace: cloned as they come). One host sync; the totals of every column
+        over this rank's chunks in order, then over the ranks in rank order."""
+        import numpy as np
+        host = torch.cat([r.reshape(-1, width) for r in rows]).cpu().numpy().astype(np.float64)
+        mine = np.cumsum(host, axis=0)[-1] if len(host) else np.zeros(width)
+        every = self.comm.all_gather_object(mine.tolist())
+        return np.cumsum(np.asarray(every, dtype=np.float64).reshape(self.world, width), axis=0)[-1], mine
+
+    def _guarded(self, produce, consume):
+        from .diloco import NonFiniteWorkers, _report, guard_decision
+        exact = self.mode == "exact"
+        totals, survivors = (self._measure_exact_first if exact else self._screen_local)(produce)
+        K = self.k_total
+        rep = self.last_stats
+        dropped = [k for k in range(K) if k not in survivors]
+        if exact and dropped:                   # measured again over the survivors, as diloco._guard_pass
+            final = self._measure_exact(survivors)
+            again = _report(final)
+            rep["grad_norm"], rep["nonfinite_mean"] = again["grad_norm"], again["nonfinite_mean"]
+            if again["cos_to_mean"] is not None:
+                cos = [float("nan")] * K
+                for j, k in enumerate(survivors):
+                    cos[k] = again["cos_to_mean"][j]
+                rep["cos_to_mean"] = cos
+            self._exact_idx = survivors
+        elif exact:
+            final = totals
+        else:
+            # phase 1 over the survivors and every exchange, all waited for; then the mean's
+            # statistics from what the owners hold
+            if dropped:
+                lo = self.rank * self.k_local
+                self._phase1 = ([k - lo for k in survivors if lo <= k < lo + self.k_local], len(survivors))
+            for ws in [produce(b, e) for b, e in self.buckets]:
+                for w in ws:
+                    w.wait()
+            rows = []
+            for b, e, s0, s1, _, _ in self._owned():
+                parts = ([self._acc_out(b, e)] if self.mode == "reduce"
+                         else list(self.acc_recv[b:e].view(self.world, s1 - s0)))
+                rows.append(torch.as_tensor(self._launch(self.kernels.partial_sum_stats, parts, self.theta_buf.dtype,
+                                                         self._stats_plan(s1 - s0))).clone())
+            t, _ = self._rank_totals(rows, 2)
+            totals["S_mm"], totals["nonfinite_mean"] = float(t[0]), int(t[1])
+            rep.update(_report(totals))
+            final = dict(totals, nonfinite=[int(totals["nonfinite"][k]) for k in survivors])
+        rep["dropped"] = dropped
+        try:
+            _, clip = guard_decision(final, self.guard)
+        except NonFiniteWorkers as err:         # the survivors' view -> every worker's counts
+            raise NonFiniteWorkers(str(err), totals["nonfinite"], final["nonfinite_mean"], survivors) from None
+        if clip is None:                        # cannot happen: every survivor was finite
+            raise EdtError("the survivors' statistics flagged a worker")
+        rep["clip_coef"] = self._clip = clip
+        return [consume(*owned) for owned in self._owned()]
+
+    def _screen_local(self, produce):
+        """Reduce schedules, before any exchange: edt_delta_stats over the local workers and the
+        whole arena gives every worker's S_kk and non-finite count (its local-mean columns are
+        ignored: the mean is not known where the deltas are); gathered, global worker index
+        rank * K_local + j; the policy screens the workers with nothing in flight."""
+        import numpy as np
+        from .diloco import _report, guard_decision
+        kl = self.k_local
+        rows = torch.as_tensor(self._launch(self.kernels.delta_stats, self.theta_buf, list(self.worker_bufs),
+                                            self._stats_plan(self.n_pad)))
+        host = rows.reshape(-1, 3 * kl + 2).cpu().numpy().astype(np.float64)     # host sync 1 of 2
+        t = np.cumsum(host, axis=0)[-1]
+        cols = _ops.stats_columns(kl)
+        every = self.comm.all_gather_object((t[cols["S_kk"]].tolist(), t[cols["nonfinite"]].tolist()))
+        totals = {"S_mm": 0.0, "S_kk": np.asarray([x for skk, _ in every for x in skk], dtype=np.float64),
+                  "S_km": None, "nonfinite_mean": 0,
+                  "nonfinite": np.asarray([x for _, nf in every for x in nf], dtype=np.float64).astype(np.int64)}
+        self.last_stats = dict(_report(totals), clip_coef=None, dropped=[])
+        survivors, _ = guard_decision(totals, self.guard)
+        return totals, list(survivors)
+
+    def _measure_exact(self, idx):
+        """exact: edt_delta_stats on every owned shard with the received slices of workers `idx`
+        (all the all-to-alls have been waited for) -> the totals over every rank's shards."""
+        import numpy as np
+        K = len(idx)
+        rows = []
+        for b, e, s0, s1, _, _ in self._owned():
+            rv = [r[b:e].view(self.world, s1 - s0) for r in self.recv]
+            shards = [rv[j][src] for src in range(self.world) for j in range(self.k_local)]
+            rows.append(torch.as_tensor(self._launch(self.kernels.delta_stats, self.theta_buf[s0:s1],
+                                                     [shards[i] for i in idx], self._stats_plan(s1 - s0))).clone())
+        t, _ = self._rank_totals(rows, 3 * K + 2)
+        cols = _ops.stats_columns(K)
+        return {"S_mm": float(t[0]), "S_kk": t[cols["S_kk"]].copy(), "S_km": t[cols["S_km"]].copy() if K <= 8 else None,
+                "nonfinite_mean": int(t[2 * K + 1]), "nonfinite": t[cols["nonfinite"]].astype(np.int64)}
+
+    def _measure_exact_first(self, produce):
+        from .diloco import _report, guard_decision
+        for ws in [produce(b, e) for b, e in self.buckets]:
+            for w in ws:
+                w.wait()
+        totals = self._measure_exact(list(range(self.k_total)))
+        self.last_stats = dict(_report(totals), clip_coef=None, dropped=[])
+        survivors, _ = guard_decision(totals, self.guard)
+        return totals, list(survivors)
+
     def _refresh_workers(self, b, e):
         """Bucket [b, e) of every local worker arena <- round_w(theta) (torch copy_: RNE), theta
         read once (edt_broadcast_theta); its gather has been waited for."""
@@ -354,9 +548,18 @@ class ShardedOuterSync:
             d.copy_(self.theta_buf[b:e])
 
     def _partial(self, b, e):
-        """Phase 1 of the fp32 reduce schedules: the local workers' partial sum of bucket [b, e)."""
-        self._launch(self.kernels.delta_partial, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
-                     self.k_total, self.acc[b:e], False)
+        """Phase 1 of the fp32 reduce schedules: the local workers' partial sum of bucket [b, e).
+        After a guarded drop (`_phase1`): over this rank's surviving workers, divided by the number
+        of survivors in all; a rank with none contributes a zero partial."""
+        workers, k_total = self.worker_bufs, self.k_total
+        if self._phase1 is not None:
+            local, k_total = self._phase1
+            workers = [self.worker_bufs[j] for j in local]
+            if not workers:
+                self.acc[b:e].zero_()
+                return
+        self._launch(self.kernels.delta_partial, self.theta_buf[b:e], [w[b:e] for w in workers],
+                     k_total, self.acc[b:e], False)
 
     # reduce: reduce-scatter each bucket's partial as soon as it is ready; SGD on the owned shard
     def _produce_reduce(self, b, e):
@@ -364,8 +567,12 @@ class ShardedOuterSync:
         return [self.comm.reduce_scatter(self._acc_out(b, e), self.acc[b:e], async_op=True)]
 
     def _consume_reduce(self, b, e, s0, s1, mom, sl):
-        self._launch(self.kernels.sgd_apply, self.theta_buf[s0:s1], self._acc_out(b, e), mom, self.has_momentum,
-                     self.lr, self.momentum, self.nesterov)
+        if self._clip != 1.0:              # a guarded step that clips
+            self._launch(self.kernels.sgd_apply_scaled, self.theta_buf[s0:s1], self._acc_out(b, e), mom,
+                         self.has_momentum, self.lr, self.momentum, self.nesterov, self._clip)
+        else:
+            self._launch(self.kernels.sgd_apply, self.theta_buf[s0:s1], self._acc_out(b, e), mom, self.has_momentum,
+                         self.lr, self.momentum, self.nesterov)
         return self._gather(b, e, s0, s1)
 
     # reduce_ordered: the partial of bucket [b, e) is laid out [dest rank][shard]; the all-to-all
@@ -418,6 +625,15 @@ class ShardedOuterSync:
         rv = [r[b:e].view(self.world, s1 - s0) for r in self.recv]
         # global worker k = src * K_local + j: the reference's worker order
         shards = [rv[j][src] for src in range(self.world) for j in range(self.k_local)]
+        if self._exact_idx is not None:    # a guarded step: the workers the guard kept
+            shards = [shards[i] for i in self._exact_idx]
+        if self._clip != 1.0:              # and clipped: the scaled step, then the unfused rounding copy
+            tail = {} if self.tail_bits is None else {"tail_bits": self.tail_bits[s0 // 8:(s1 + 7) // 8]}
+            self._launch(k.outer_step_scaled, self.theta_buf[s0:s1], shards, mom, self.has_momentum, self.lr,
+                         self.momentum, self.nesterov, self._clip, **tail)
+            if self.broadcast == "workers":
+                return self._gather_to_workers(b, e, s0, s1, rounded=False)
+            return self._gather(b, e, s0, s1)
         # broadcast="workers": the HIP kernel also stores the new shard, rounded to the worker
         # dtype, into local worker 0's arena (its bucket has been sent) — the rounding copy fused
         # into the step
@@ -436,13 +652,16 @@ class ShardedOuterSync:
     def _sgd_sum(self, theta, parts, mom):
         """SGD from the shard's per-rank partials, summed in rank order."""
         k = self.kernels
+        clip = () if self._clip == 1.0 else (self._clip,)        # a guarded step that clips: the scaled entries
         if hasattr(k, "sgd_apply_sum"):
-            k.sgd_apply_sum(theta, parts, mom, self.has_momentum, self.lr, self.momentum, self.nesterov)
+            fn = k.sgd_apply_sum_scaled if clip else k.sgd_apply_sum
+            fn(theta, parts, mom, self.has_momentum, self.lr, self.momentum, self.nesterov, *clip)
             return
         total = parts[0].clone()             # stand-in kernels (CPU tests): the same order in torch
         for p in parts[1:]:
             total.add_(p)
-        k.sgd_apply(theta, total, mom, self.has_momentum, self.lr, self.momentum, self.nesterov)
+        fn = k.sgd_apply_scaled if clip else k.sgd_apply
+        fn(theta, total, mom, self.has_momentum, self.lr, self.momentum, self.nesterov, *clip)
 
     def _acc_out(self, b, e):
         """Reduce-scatter destination for bucket [b, e): this rank's slice of the acc buffer

@@ -251,6 +251,66 @@ def sgd_apply_sum(theta: torch.Tensor, accs: list[torch.Tensor], momentum: torch
                                   L.stream_ptr(theta.device)), "edt_sgd_apply_sum")
 
 
+def sgd_apply_scaled(theta: torch.Tensor, acc: torch.Tensor, momentum: torch.Tensor | None,
+                     has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool, grad_scale: float) -> None:
+    """`sgd_apply` with a clipped pseudo-gradient (edt_sgd_apply_scaled): grad = round((-round(acc)) *
+    grad_scale), one fp32 multiply, then the unchanged SGD update. grad_scale: finite, in [0, 1];
+    1.0 gives sgd_apply's bits."""
+    lib = L.lib()
+    L.require_device(theta, acc, momentum)
+    if acc.dtype != torch.float32 or acc.numel() != theta.numel():
+        raise L.EdtError("acc must be a float32 buffer of theta's size")
+    _check_momentum(momentum, theta)
+    L.check(lib.edt_sgd_apply_scaled(L.ptr(theta), L.dtype_code(theta), L.ptr(acc), L.ptr(momentum),
+                                     int(has_momentum), theta.numel(), float(lr), float(momentum_coef),
+                                     int(nesterov), float(grad_scale), L.stream_ptr(theta.device)),
+            "edt_sgd_apply_scaled")
+
+
+def sgd_apply_sum_scaled(theta: torch.Tensor, accs: list[torch.Tensor], momentum: torch.Tensor | None,
+                         has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool,
+                         grad_scale: float) -> None:
+    """`sgd_apply_sum` with a clipped pseudo-gradient (edt_sgd_apply_sum_scaled; sgd_apply_scaled's
+    rule on the rank-ordered sum)."""
+    lib = L.lib()
+    L.require_device(theta, momentum, *accs)
+    if not accs or any(a.dtype != torch.float32 or a.numel() != theta.numel() for a in accs):
+        raise L.EdtError("accs: fp32 buffers of theta's size")
+    _check_momentum(momentum, theta)
+    L.check(lib.edt_sgd_apply_sum_scaled(L.ptr(theta), L.dtype_code(theta), L.ptr_array(accs), len(accs),
+                                         L.ptr(momentum), int(has_momentum), theta.numel(), float(lr),
+                                         float(momentum_coef), int(nesterov), float(grad_scale),
+                                         L.stream_ptr(theta.device)), "edt_sgd_apply_sum_scaled")
+
+
+def partial_sum_stats(accs: list[torch.Tensor], gdt_like, plan: "SlerpPlan") -> torch.Tensor:
+    """Per-chunk statistics of the mean pseudo-gradient `sgd_apply_sum(theta, accs, ...)` (one
+    partial: `sgd_apply`) would apply, read only (edt_partial_sum_stats): float64 [plan.nchunks, 2]
+    on the device, S_mm | nonfinite_mean, of m = round(((acc_0 + acc_1) + ...)) in the dtype of
+    `gdt_like` (theta, or its dtype), fp64 sums in the canonical chunk-sum order; what is not finite
+    is left out of S_mm and counted. plan: `make_slerp_plan(seg_offsets, device)` over the shard
+    (absolute starts; the last offset is the partials' size). The result is a view of the pooled
+    workspace (`_scratch`): read it before the next call on this stream overwrites it."""
+    lib = L.lib()
+    if not accs:
+        raise L.EdtError("no partials")
+    L.require_device(*accs)
+    n = accs[0].numel()
+    if any(a.dtype != torch.float32 or a.numel() != n for a in accs):
+        raise L.EdtError("accs: fp32 buffers of one size")
+    if len(accs) > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"the statistics pass takes at most {L.EDT_MAX_WORKERS} partials")
+    if plan.relative or plan.seg_offsets[0] != 0 or plan.seg_offsets[-1] != n:
+        raise L.EdtError("the chunk plan must cover the partials' elements with absolute starts")
+    dev = accs[0].device
+    if plan.chunks.device != dev:
+        raise L.EdtError("the chunk plan lives on another device")
+    out = _scratch(dev, int(lib.edt_partial_sum_stats_doubles(plan.nchunks)))
+    L.check(lib.edt_partial_sum_stats(L.ptr_array(accs), len(accs), L.dtype_code(gdt_like), n, L.ptr(plan.chunks),
+                                      plan.nchunks, L.ptr(out), L.stream_ptr(dev)), "edt_partial_sum_stats")
+    return out[:plan.nchunks * 2].view(plan.nchunks, 2)
+
+
 # Argument checks the sharded wrappers share: one message each, whichever wrapper raises it.
 def _check_momentum(momentum, theta: torch.Tensor) -> None:
     if momentum is not None and (momentum.numel() != theta.numel() or momentum.dtype != theta.dtype):

@@ -182,6 +182,31 @@ int edt_sgd_apply(void* theta_g, int gdt, const float* acc_f32, void* momentum, 
 int edt_sgd_apply_sum(void* theta_g, int gdt, const float* const* acc_f32, int nacc, void* momentum,
                       int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream);
 
+/* The two sharded SGD entries with a clipped pseudo-gradient (edt_outer_step_scaled's rule):
+ * grad = round_g((-a) * grad_scale), a the rounded sum edt_sgd_apply(_sum) negates — one fp32
+ * multiply rounded to theta's dtype, then the unchanged SGD update. grad_scale must be finite and in
+ * [0, 1] (EDT_ERR_ARG otherwise, nothing written); 1.0f gives the unscaled entry's bits. */
+int edt_sgd_apply_sum_scaled(void* theta_g, int gdt, const float* const* acc_f32, int nacc, void* momentum,
+                             int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                             float grad_scale, void* stream);
+int edt_sgd_apply_scaled(void* theta_g, int gdt, const float* acc_f32, void* momentum, int has_momentum,
+                         uint64_t n, double lr, double momentum_coef, int nesterov, float grad_scale, void* stream);
+
+/* Statistics of the mean pseudo-gradient a shard owner is about to apply, read-only: per element
+ *   m = round_g(((acc_0 + acc_1) + ...) + acc_{nacc-1})     (fp32 adds in that order)
+ * which is the value edt_sgd_apply_sum (nacc partials) or edt_sgd_apply (nacc = 1: the reduced
+ * shard) negates into the gradient. chunk_desc (device): nchunks chunks in edt_slerp_make_chunks'
+ * format over [0, n), the same for every partial. out (device, 8-byte aligned,
+ * edt_partial_sum_stats_doubles(nchunks) doubles): first the chunk rows [nchunks][2]
+ *   S_mm = sum m^2 | nonfinite_mean
+ * then the pass's row scratch. fp64 sums in the canonical chunk-sum order, with edt_delta_stats'
+ * tile, lane and tree mapping; an element whose m is not finite adds nothing to S_mm and is
+ * counted. Partials off a 16-byte boundary take scalar loads; the sums are the same.
+ * 1 <= nacc <= EDT_MAX_WORKERS, gdt EDT_F32 or EDT_BF16. */
+uint64_t edt_partial_sum_stats_doubles(int64_t nchunks);
+int edt_partial_sum_stats(const float* const* acc_f32, int nacc, int gdt, uint64_t n, const uint64_t* chunk_desc,
+                          int64_t nchunks, double* out, void* stream);
+
 /* ---- block-quantized partial exchange (the sharded step's opt-in "reduce_q" schedule) --------
  * The reference moves checkpoints over a shared disk (EDT_LM/diloco.py:231-235, 302-308) and has
  * no wire format; reduce_ordered ships each rank's pseudo-gradient partial as fp32. These entries
