@@ -70,7 +70,7 @@ on the comm stream overlaps the HBM-bound kernels on the compute stream:
                          across the ranks before theta is touched: every rank forms the
                          same float64 totals in one fixed order (its buckets and chunks in order, then
                          the ranks in rank order after an all_gather_object) and takes the same
-                         diloco.guard_decision. The reduce schedules screen the local workers before
+                         guard.guard_decision. The reduce schedules screen the local workers before
                          the exchange (edt_delta_stats: S_kk and the non-finite counts) and measure
                          the mean on the owned shards after it (edt_partial_sum_stats), clipping with
                          edt_sgd_apply(_sum)_scaled; exact runs edt_delta_stats on the received slices
@@ -86,13 +86,17 @@ Every rank holds 1/N of the momentum and owns contiguous shards of every bucket.
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from . import ops as _ops
 from ._lib import EdtError
 from .collectives import Collectives, TorchCollectives
 from .diloco import check_sgd_hparams
+from .guard import (NonFiniteWorkers, OuterGuard, fold_remeasured, guard_decision, report, sequential_total,
+                    totals_from_row)
 from .params import ParamArena, ParamLayout
 from .tracing import trange, traced
 
@@ -104,6 +108,27 @@ def _timing_event():
 _Q_BITS = {"mxfp8": 8, "mxfp4": 4}       # element bits of the reduce_q wire formats
 
 
+class _Verdict(NamedTuple):
+    """What the guard decided for one step, handed to the phases that act on it and kept nowhere."""
+    local: list | None         # this rank's surviving local workers (None: all of them)
+    divisor: int | None        # how many workers phase 1 divides by (None: k_total)
+    survivors: list | None     # exact: the surviving global workers (None: all of them)
+    clip: float                # the factor on the mean pseudo-gradient; 1.0: the plain entries
+
+
+_NO_GUARD = _Verdict(None, None, None, 1.0)      # every worker, unclipped: what an unguarded step passes
+
+
+def _scaled(name: str) -> str:
+    return name + "_scaled"
+
+
+def _entry(name: str, clip: float):
+    """The kernels' entry of a step and its trailing arguments: `name` itself at exactly 1.0, else
+    its scaled form with the coefficient."""
+    return (name, ()) if clip == 1.0 else (_scaled(name), (clip,))
+
+
 class ShardedOuterSync:
     def __init__(self, layout: ParamLayout, theta_dtype: torch.dtype, worker_dtype: torch.dtype,
                  k_local: int, device, lr: float = 0.7, momentum: float = 0.9, nesterov: bool = True,
@@ -112,7 +137,7 @@ class ShardedOuterSync:
                  cpu_tails: tuple[int, int] | None = None, wire_format: str = "mxfp8",
                  error_feedback: bool = True, gather_format: str | None = None, rounding: str = "nearest",
                  seed: int = 0, guard=None):
-        """guard: a diloco.OuterGuard — every step is measured, screened and clipped across the ranks
+        """guard: a guard.OuterGuard — every step is measured, screened and clipped across the ranks
         before theta is touched (`_guarded`, `last_stats`); None: nothing changes.
         mode="reduce_q": `wire_format` picks the element format of the quantized partials and
         `error_feedback` keeps `self.residual` — this rank's fp32 quantization error (n_pad
@@ -177,9 +202,6 @@ class ShardedOuterSync:
         self.q_step = 0                # stochastic rounding: the step counter of the random bits
         self.guard = guard
         self.last_stats = None         # the last guarded step's report, identical on every rank
-        # what a guarded step hands its phases (reset after every step): the local survivors and
-        # divisor of phase 1, the surviving global workers of the exact step, the clip coefficient
-        self._phase1, self._exact_idx, self._clip = None, None, 1.0
         self._guard_plans = {}
         if guard is not None:
             self._check_guard()
@@ -260,7 +282,6 @@ class ShardedOuterSync:
 
     def _check_guard(self):
         """The constructor's refusals of guard=: each says what is missing."""
-        from .diloco import OuterGuard
         if not isinstance(self.guard, OuterGuard):
             raise TypeError("guard must be an OuterGuard")
         if self.mode == "reduce_q":
@@ -273,16 +294,21 @@ class ShardedOuterSync:
         if self.k_total > 64:
             raise EdtError(f"a guarded step takes at most 64 workers in all, not {self.k_total}")
         k = self.kernels
-        if self.mode == "exact":
-            need = ["make_slerp_plan", "delta_stats", "outer_step_scaled"]
-        else:
-            need = ["make_slerp_plan", "delta_stats", "partial_sum_stats", "sgd_apply_scaled"]
-            if self.mode == "reduce_ordered" and hasattr(k, "sgd_apply_sum"):
-                need[-1] = "sgd_apply_sum_scaled"
+        need = ["make_slerp_plan", "delta_stats"] + ([] if self.mode == "exact" else ["partial_sum_stats"])
+        need.append(_scaled(self._step_name()))
         missing = [m for m in need if not hasattr(k, m)]
         if missing:
             raise EdtError(f"guard= with mode={self.mode!r} needs kernels that provide {need}; "
                            f"{type(k).__name__ if not hasattr(k, '__name__') else k.__name__} lacks {missing}")
+
+    def _step_name(self) -> str:
+        """The entry that steps an owned shard in this schedule, before `_entry` picks its plain or
+        scaled form. Without sgd_apply_sum (stand-in kernels) reduce_ordered sums in torch."""
+        if self.mode == "exact":
+            return "outer_step"
+        if self.mode == "reduce_ordered" and hasattr(self.kernels, "sgd_apply_sum"):
+            return "sgd_apply_sum"
+        return "sgd_apply"
 
     def guard_bytes(self) -> int:
         """Algorithmic HBM bytes the guard adds to one step on this rank (no drop; kernel_bytes()
@@ -375,17 +401,14 @@ class ShardedOuterSync:
         if self.guard is not None:
             # measured, screened and clipped first (_guarded): every exchange is waited for before
             # the decision, so nothing below runs on a step the guard refuses
-            try:
-                gathers = self._guarded(produce, consume)
-            finally:
-                self._phase1, self._exact_idx, self._clip = None, None, 1.0
+            gathers = self._guarded(produce, consume)
         else:
-            works = [produce(b, e) for b, e in self.buckets]
+            works = [produce(b, e, _NO_GUARD) for b, e in self.buckets]
             gathers = []
-            for (b, e, s0, s1, mom, sl), ws in zip(self._owned(), works):
+            for owned, ws in zip(self._owned(), works):
                 for w in ws:
                     w.wait()
-                gathers.append(consume(b, e, s0, s1, mom, sl))
+                gathers.append(consume(*owned, _NO_GUARD))
         if self.mode == "reduce_q" and self.gather_format is not None:
             # phase 3: as each bucket's updates land, every rank adds the same D(q) to its replica
             gf = self.gather_format
@@ -423,7 +446,7 @@ class ShardedOuterSync:
     # One rule: every rank forms the same float64 totals from the same numbers in the same order —
     # per rank its buckets in order and their chunks in order (cumsum), then the ranks in rank order
     # after an all_gather_object of the per-rank totals, never an all-reduce in the library's own
-    # order — and calls the same pure diloco.guard_decision on them. So every rank steps, or every
+    # order — and calls the same pure guard.guard_decision on them. So every rank steps, or every
     # rank raises the same exception, with every issued collective waited for.
 
     def _stats_plan(self, n):
@@ -436,106 +459,99 @@ class ShardedOuterSync:
         """rows: this rank's per-bucket row blocks (device, consumed before the next statistics
         call reuses the workspace: cloned as they come). One host sync; the totals of every column
         over this rank's chunks in order, then over the ranks in rank order."""
-        import numpy as np
-        host = torch.cat([r.reshape(-1, width) for r in rows]).cpu().numpy().astype(np.float64)
-        mine = np.cumsum(host, axis=0)[-1] if len(host) else np.zeros(width)
-        every = self.comm.all_gather_object(mine.tolist())
-        return np.cumsum(np.asarray(every, dtype=np.float64).reshape(self.world, width), axis=0)[-1], mine
+        mine = sequential_total(torch.cat([r.reshape(-1, width) for r in rows]).cpu().numpy(), width)
+        return sequential_total(self.comm.all_gather_object(mine.tolist()), width)
+
+    def _exchange(self, produce, v: _Verdict) -> None:
+        """Every bucket's produce, then every handle waited for: nothing is in flight afterwards."""
+        for ws in [produce(b, e, v) for b, e in self.buckets]:
+            for w in ws:
+                w.wait()
+
+    def _screen(self, totals: dict) -> list:
+        """A step's first statistics, recorded and screened (may refuse) -> the surviving workers."""
+        self.last_stats = dict(report(totals), clip_coef=None, dropped=[])
+        return list(guard_decision(totals, self.guard)[0])
+
+    def _verdict(self, survivors: list, clip: float) -> _Verdict:
+        if len(survivors) == self.k_total:
+            return _NO_GUARD._replace(clip=clip)
+        lo = self.rank * self.k_local
+        return _Verdict([k - lo for k in survivors if lo <= k < lo + self.k_local], len(survivors), survivors, clip)
 
     def _guarded(self, produce, consume):
-        from .diloco import NonFiniteWorkers, _report, guard_decision
-        exact = self.mode == "exact"
-        totals, survivors = (self._measure_exact_first if exact else self._screen_local)(produce)
-        K = self.k_total
+        """The tail both schedule families share. Each family returns the totals over all workers,
+        the totals of what will be applied and the survivors, with every exchange waited for."""
+        totals, final, survivors = (self._guard_exact if self.mode == "exact" else self._guard_reduce)(produce)
         rep = self.last_stats
-        dropped = [k for k in range(K) if k not in survivors]
-        if exact and dropped:                   # measured again over the survivors, as diloco._guard_pass
-            final = self._measure_exact(survivors)
-            again = _report(final)
-            rep["grad_norm"], rep["nonfinite_mean"] = again["grad_norm"], again["nonfinite_mean"]
-            if again["cos_to_mean"] is not None:
-                cos = [float("nan")] * K
-                for j, k in enumerate(survivors):
-                    cos[k] = again["cos_to_mean"][j]
-                rep["cos_to_mean"] = cos
-            self._exact_idx = survivors
-        elif exact:
-            final = totals
-        else:
-            # phase 1 over the survivors and every exchange, all waited for; then the mean's
-            # statistics from what the owners hold
-            if dropped:
-                lo = self.rank * self.k_local
-                self._phase1 = ([k - lo for k in survivors if lo <= k < lo + self.k_local], len(survivors))
-            for ws in [produce(b, e) for b, e in self.buckets]:
-                for w in ws:
-                    w.wait()
-            rows = []
-            for b, e, s0, s1, _, _ in self._owned():
-                parts = ([self._acc_out(b, e)] if self.mode == "reduce"
-                         else list(self.acc_recv[b:e].view(self.world, s1 - s0)))
-                rows.append(torch.as_tensor(self._launch(self.kernels.partial_sum_stats, parts, self.theta_buf.dtype,
-                                                         self._stats_plan(s1 - s0))).clone())
-            t, _ = self._rank_totals(rows, 2)
-            totals["S_mm"], totals["nonfinite_mean"] = float(t[0]), int(t[1])
-            rep.update(_report(totals))
-            final = dict(totals, nonfinite=[int(totals["nonfinite"][k]) for k in survivors])
-        rep["dropped"] = dropped
+        rep["dropped"] = [k for k in range(self.k_total) if k not in survivors]
         try:
             _, clip = guard_decision(final, self.guard)
         except NonFiniteWorkers as err:         # the survivors' view -> every worker's counts
             raise NonFiniteWorkers(str(err), totals["nonfinite"], final["nonfinite_mean"], survivors) from None
         if clip is None:                        # cannot happen: every survivor was finite
             raise EdtError("the survivors' statistics flagged a worker")
-        rep["clip_coef"] = self._clip = clip
-        return [consume(*owned) for owned in self._owned()]
+        rep["clip_coef"] = clip
+        v = self._verdict(survivors, clip)
+        return [consume(*owned, v) for owned in self._owned()]
 
-    def _screen_local(self, produce):
-        """Reduce schedules, before any exchange: edt_delta_stats over the local workers and the
+    def _guard_reduce(self, produce):
+        """Reduce schedules. Before any exchange, edt_delta_stats over the local workers and the
         whole arena gives every worker's S_kk and non-finite count (its local-mean columns are
         ignored: the mean is not known where the deltas are); gathered, global worker index
-        rank * K_local + j; the policy screens the workers with nothing in flight."""
-        import numpy as np
-        from .diloco import _report, guard_decision
-        kl = self.k_local
+        rank * K_local + j; the policy screens the workers with nothing in flight. Then phase 1 over
+        the survivors and every exchange, and the mean's statistics from what the owners hold."""
+        kl, K = self.k_local, self.k_total
         rows = torch.as_tensor(self._launch(self.kernels.delta_stats, self.theta_buf, list(self.worker_bufs),
                                             self._stats_plan(self.n_pad)))
-        host = rows.reshape(-1, 3 * kl + 2).cpu().numpy().astype(np.float64)     # host sync 1 of 2
-        t = np.cumsum(host, axis=0)[-1]
+        t = sequential_total(rows.cpu().numpy(), 3 * kl + 2)                     # host sync 1 of 2
         cols = _ops.stats_columns(kl)
         every = self.comm.all_gather_object((t[cols["S_kk"]].tolist(), t[cols["nonfinite"]].tolist()))
-        totals = {"S_mm": 0.0, "S_kk": np.asarray([x for skk, _ in every for x in skk], dtype=np.float64),
-                  "S_km": None, "nonfinite_mean": 0,
-                  "nonfinite": np.asarray([x for _, nf in every for x in nf], dtype=np.float64).astype(np.int64)}
-        self.last_stats = dict(_report(totals), clip_coef=None, dropped=[])
-        survivors, _ = guard_decision(totals, self.guard)
-        return totals, list(survivors)
+        row, cols = np.zeros(3 * K + 2), _ops.stats_columns(K)
+        row[cols["S_kk"]] = [x for skk, _ in every for x in skk]
+        row[cols["nonfinite"]] = [x for _, nf in every for x in nf]
+        # the mean's columns stay zero until the exchange, and no schedule here forms S_km
+        totals = dict(totals_from_row(row, K), S_km=None)
+        survivors = self._screen(totals)
+        self._exchange(produce, self._verdict(survivors, 1.0))
+        rows = []
+        for b, e, s0, s1, _, _ in self._owned():
+            parts = ([self._acc_out(b, e)] if self.mode == "reduce"
+                     else list(self.acc_recv[b:e].view(self.world, s1 - s0)))
+            rows.append(torch.as_tensor(self._launch(self.kernels.partial_sum_stats, parts, self.theta_buf.dtype,
+                                                     self._stats_plan(s1 - s0))).clone())
+        t = self._rank_totals(rows, 2)                                           # host sync 2 of 2
+        totals["S_mm"], totals["nonfinite_mean"] = float(t[0]), int(t[1])
+        self.last_stats.update(report(totals))
+        return totals, dict(totals, nonfinite=[int(totals["nonfinite"][k]) for k in survivors]), survivors
+
+    def _guard_exact(self, produce):
+        """exact: every all-to-all first, then edt_delta_stats on the received slices; after a drop
+        the survivors are measured again, as diloco._guard_pass does."""
+        self._exchange(produce, _NO_GUARD)
+        totals = final = self._measure_exact(list(range(self.k_total)))
+        survivors = self._screen(totals)
+        if len(survivors) < self.k_total:
+            final = self._measure_exact(survivors)
+            fold_remeasured(self.last_stats, report(final), survivors, self.k_total)
+        return totals, final, survivors
 
     def _measure_exact(self, idx):
         """exact: edt_delta_stats on every owned shard with the received slices of workers `idx`
         (all the all-to-alls have been waited for) -> the totals over every rank's shards."""
-        import numpy as np
         K = len(idx)
         rows = []
         for b, e, s0, s1, _, _ in self._owned():
-            rv = [r[b:e].view(self.world, s1 - s0) for r in self.recv]
-            shards = [rv[j][src] for src in range(self.world) for j in range(self.k_local)]
+            shards = self._received(b, e)
             rows.append(torch.as_tensor(self._launch(self.kernels.delta_stats, self.theta_buf[s0:s1],
                                                      [shards[i] for i in idx], self._stats_plan(s1 - s0))).clone())
-        t, _ = self._rank_totals(rows, 3 * K + 2)
-        cols = _ops.stats_columns(K)
-        return {"S_mm": float(t[0]), "S_kk": t[cols["S_kk"]].copy(), "S_km": t[cols["S_km"]].copy() if K <= 8 else None,
-                "nonfinite_mean": int(t[2 * K + 1]), "nonfinite": t[cols["nonfinite"]].astype(np.int64)}
+        return totals_from_row(self._rank_totals(rows, 3 * K + 2), K)
 
-    def _measure_exact_first(self, produce):
-        from .diloco import _report, guard_decision
-        for ws in [produce(b, e) for b, e in self.buckets]:
-            for w in ws:
-                w.wait()
-        totals = self._measure_exact(list(range(self.k_total)))
-        self.last_stats = dict(_report(totals), clip_coef=None, dropped=[])
-        survivors, _ = guard_decision(totals, self.guard)
-        return totals, list(survivors)
+    def _received(self, b, e):
+        """exact: the owned shard's slice of every worker as the all-to-alls of bucket [b, e) left
+        it, in the reference's worker order (global worker k = src * K_local + j)."""
+        rv = [r[b:e].view(self.world, (e - b) // self.world) for r in self.recv]
+        return [rv[j][src] for src in range(self.world) for j in range(self.k_local)]
 
     def _refresh_workers(self, b, e):
         """Bucket [b, e) of every local worker arena <- round_w(theta) (torch copy_: RNE), theta
@@ -547,14 +563,13 @@ class ShardedOuterSync:
         for d in dst:                        # stand-in kernels (CPU tests): the same copies in torch
             d.copy_(self.theta_buf[b:e])
 
-    def _partial(self, b, e):
+    def _partial(self, b, e, v: _Verdict):
         """Phase 1 of the fp32 reduce schedules: the local workers' partial sum of bucket [b, e).
-        After a guarded drop (`_phase1`): over this rank's surviving workers, divided by the number
+        After a guarded drop (`v.local`): over this rank's surviving workers, divided by the number
         of survivors in all; a rank with none contributes a zero partial."""
         workers, k_total = self.worker_bufs, self.k_total
-        if self._phase1 is not None:
-            local, k_total = self._phase1
-            workers = [self.worker_bufs[j] for j in local]
+        if v.local is not None:
+            workers, k_total = [self.worker_bufs[j] for j in v.local], v.divisor
             if not workers:
                 self.acc[b:e].zero_()
                 return
@@ -562,40 +577,38 @@ class ShardedOuterSync:
                      k_total, self.acc[b:e], False)
 
     # reduce: reduce-scatter each bucket's partial as soon as it is ready; SGD on the owned shard
-    def _produce_reduce(self, b, e):
-        self._partial(b, e)
+    def _produce_reduce(self, b, e, v):
+        self._partial(b, e, v)
         return [self.comm.reduce_scatter(self._acc_out(b, e), self.acc[b:e], async_op=True)]
 
-    def _consume_reduce(self, b, e, s0, s1, mom, sl):
-        if self._clip != 1.0:              # a guarded step that clips
-            self._launch(self.kernels.sgd_apply_scaled, self.theta_buf[s0:s1], self._acc_out(b, e), mom,
-                         self.has_momentum, self.lr, self.momentum, self.nesterov, self._clip)
-        else:
-            self._launch(self.kernels.sgd_apply, self.theta_buf[s0:s1], self._acc_out(b, e), mom, self.has_momentum,
-                         self.lr, self.momentum, self.nesterov)
+    def _consume_reduce(self, b, e, s0, s1, mom, sl, v):
+        name, scale = _entry(self._step_name(), v.clip)
+        self._launch(getattr(self.kernels, name), self.theta_buf[s0:s1], self._acc_out(b, e), mom, self.has_momentum,
+                     self.lr, self.momentum, self.nesterov, *scale)
         return self._gather(b, e, s0, s1)
 
     # reduce_ordered: the partial of bucket [b, e) is laid out [dest rank][shard]; the all-to-all
     # delivers it as [src rank][shard], and the owned shard's N partials are summed in rank order
-    def _produce_reduce_ordered(self, b, e):
-        self._partial(b, e)
+    def _produce_reduce_ordered(self, b, e, v):
+        self._partial(b, e, v)
         return [self.comm.all_to_all(self.acc_recv[b:e], self.acc[b:e], async_op=True)]
 
-    def _consume_reduce_ordered(self, b, e, s0, s1, mom, sl):
-        self._launch(self._sgd_sum, self.theta_buf[s0:s1], list(self.acc_recv[b:e].view(self.world, s1 - s0)), mom)
+    def _consume_reduce_ordered(self, b, e, s0, s1, mom, sl, v):
+        self._launch(self._sgd_sum, self.theta_buf[s0:s1], list(self.acc_recv[b:e].view(self.world, s1 - s0)), mom,
+                     v.clip)
         return self._gather(b, e, s0, s1)
 
     # reduce_q: reduce_ordered with quantized partials: phase 1 writes bucket [b, e) as `world`
     # packed regions [dest rank][payload | scales] (the fp32 partial stays in registers), the
     # all-to-all moves the bytes; phase 2 dequantizes the owned shard's N regions
-    def _produce_reduce_q(self, b, e):
+    def _produce_reduce_q(self, b, e, v):
         qb, qe = self._q_bytes(b), self._q_bytes(e)
         self._launch(self.kernels.delta_partial_q, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
                      self.k_total, self.q_send[qb:qe], (e - b) // self.world, self.wire_format,
                      None if self.residual is None else self.residual[b:e], **self._sr(0, b))
         return [self.comm.all_to_all(self.q_recv[qb:qe], self.q_send[qb:qe], async_op=True)]
 
-    def _consume_reduce_q(self, b, e, s0, s1, mom, sl):
+    def _consume_reduce_q(self, b, e, s0, s1, mom, sl, v):
         k, per = self.kernels, s1 - s0
         regions = list(self.q_recv[self._q_bytes(b):self._q_bytes(e)].view(self.world, self._q_bytes(per)))
         if self.gather_format is None:
@@ -616,52 +629,38 @@ class ShardedOuterSync:
     # exact: every bucket's all-to-all straight from the worker arenas (a worker's bucket [b, e) is
     # already laid out [dest rank][per]), one collective per local worker; as each bucket lands,
     # the single-GPU fused step on the owned shard
-    def _produce_exact(self, b, e):
+    def _produce_exact(self, b, e, v):
         return [self.comm.all_to_all(self.recv[j][b:e], wb[b:e], async_op=True)
                 for j, wb in enumerate(self.worker_bufs)]
 
-    def _consume_exact(self, b, e, s0, s1, mom, sl):
+    def _consume_exact(self, b, e, s0, s1, mom, sl, v):
         k = self.kernels
-        rv = [r[b:e].view(self.world, s1 - s0) for r in self.recv]
-        # global worker k = src * K_local + j: the reference's worker order
-        shards = [rv[j][src] for src in range(self.world) for j in range(self.k_local)]
-        if self._exact_idx is not None:    # a guarded step: the workers the guard kept
-            shards = [shards[i] for i in self._exact_idx]
-        if self._clip != 1.0:              # and clipped: the scaled step, then the unfused rounding copy
-            tail = {} if self.tail_bits is None else {"tail_bits": self.tail_bits[s0 // 8:(s1 + 7) // 8]}
-            self._launch(k.outer_step_scaled, self.theta_buf[s0:s1], shards, mom, self.has_momentum, self.lr,
-                         self.momentum, self.nesterov, self._clip, **tail)
-            if self.broadcast == "workers":
-                return self._gather_to_workers(b, e, s0, s1, rounded=False)
-            return self._gather(b, e, s0, s1)
-        # broadcast="workers": the HIP kernel also stores the new shard, rounded to the worker
+        shards = self._received(b, e)
+        if v.survivors is not None:        # a guarded step: the workers the guard kept
+            shards = [shards[i] for i in v.survivors]
+        name, scale = _entry(self._step_name(), v.clip)
+        # shards start at multiples of 64: whole bytes of the tail mask
+        tail = {} if self.tail_bits is None else {"tail_bits": self.tail_bits[s0 // 8:(s1 + 7) // 8]}
+        # broadcast="workers": the plain HIP kernel also stores the new shard, rounded to the worker
         # dtype, into local worker 0's arena (its bucket has been sent) — the rounding copy fused
-        # into the step
-        fused = self.broadcast == "workers" and k is _ops and self.tail_bits is None
-        if self.tail_bits is not None:     # shards start at multiples of 64: whole bytes
-            import functools
-            fn = functools.partial(k.outer_step, tail_bits=self.tail_bits[s0 // 8:(s1 + 7) // 8])
-        else:
-            fn = k.outer_step
-        self._launch(fn, self.theta_buf[s0:s1], shards, mom, self.has_momentum, self.lr,
-                     self.momentum, self.nesterov, *([[self.worker_bufs[0][s0:s1]]] if fused else []))
+        # into the step; the scaled and the tail forms have no fused broadcast
+        fused = self.broadcast == "workers" and k is _ops and not scale and not tail
+        self._launch(getattr(k, name), self.theta_buf[s0:s1], shards, mom, self.has_momentum, self.lr,
+                     self.momentum, self.nesterov, *scale, *([[self.worker_bufs[0][s0:s1]]] if fused else []), **tail)
         if self.broadcast == "workers":
             return self._gather_to_workers(b, e, s0, s1, rounded=fused)
         return self._gather(b, e, s0, s1)
 
-    def _sgd_sum(self, theta, parts, mom):
+    def _sgd_sum(self, theta, parts, mom, clip):
         """SGD from the shard's per-rank partials, summed in rank order."""
-        k = self.kernels
-        clip = () if self._clip == 1.0 else (self._clip,)        # a guarded step that clips: the scaled entries
-        if hasattr(k, "sgd_apply_sum"):
-            fn = k.sgd_apply_sum_scaled if clip else k.sgd_apply_sum
-            fn(theta, parts, mom, self.has_momentum, self.lr, self.momentum, self.nesterov, *clip)
-            return
-        total = parts[0].clone()             # stand-in kernels (CPU tests): the same order in torch
-        for p in parts[1:]:
-            total.add_(p)
-        fn = k.sgd_apply_scaled if clip else k.sgd_apply
-        fn(theta, total, mom, self.has_momentum, self.lr, self.momentum, self.nesterov, *clip)
+        step = self._step_name()
+        name, scale = _entry(step, clip)
+        if step == "sgd_apply":
+            total = parts[0].clone()         # stand-in kernels (CPU tests): the same order in torch
+            for p in parts[1:]:
+                total.add_(p)
+            parts = total
+        getattr(self.kernels, name)(theta, parts, mom, self.has_momentum, self.lr, self.momentum, self.nesterov, *scale)
 
     def _acc_out(self, b, e):
         """Reduce-scatter destination for bucket [b, e): this rank's slice of the acc buffer
@@ -860,7 +859,6 @@ class ShardedPopulationCrossover:
         self.kind, self.layout, self.device = kind, layout, torch.device(device)
         self.dtype, self.out_dtype = dtype, out_dtype or dtype
         self.kernels = kernels or _ops
-        import numpy as np
         self.plan = self.kernels.make_slerp_plan(layout.offsets, self.device, chunk_elems=chunk_elems)
         host = np.asarray(self.plan.chunks_host, dtype=np.int64).reshape(-1, 3)
         n, N = layout.total, self.world
@@ -993,7 +991,6 @@ class ShardedPopulationCrossover:
         the reference's coefficients of every child from them (ops.reference_coefficients): the
         children equal the reference's merges bit for bit with band < 0. Returns (coef [Q, nseg, 2],
         dots [Q, nseg]) on the device."""
-        import numpy as np
         ref.check_host()
         k, N, Q = self.kernels, self.world, len(pairs)
         plan, nseg = self.plan, self.plan.nseg

@@ -11,6 +11,7 @@ import ctypes
 import threading
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -31,36 +32,22 @@ def outer_step(theta: torch.Tensor, workers: list[torch.Tensor], momentum: torch
     there (edt_outer_step_tail); with a broadcast too, the tail step runs and then each broadcast
     buffer is copied from theta."""
     lib = L.lib()
-    if not workers:
-        raise L.EdtError("no workers")
-    L.require_device(theta, momentum, *workers, *(broadcast or []))
     n = theta.numel()
-    for w in workers:
-        if w.numel() != n or w.dtype != workers[0].dtype:
-            raise L.EdtError("every worker buffer must match theta's size and share one dtype")
-    _check_momentum(momentum, theta)
+    head = _step_head(theta, workers, momentum, has_momentum, lr, momentum_coef, nesterov, *(broadcast or []))
     if broadcast and any(b.numel() != n or b.dtype != workers[0].dtype for b in broadcast):
         raise L.EdtError("broadcast buffers must match theta's size and the workers' dtype")
     if tail_bits is not None:
         # checked first: the tail emulation is never dropped because a broadcast was asked for
-        L.require_device(tail_bits)
+        _check_tail_bits(tail_bits, n)
         if len(workers) > L.EDT_MAX_WORKERS:
             raise L.EdtError("tail emulation runs in the plain fused step (<= 64 workers)")
-        if tail_bits.dtype != torch.uint8 or tail_bits.numel() * 8 < n:
-            raise L.EdtError("tail_bits: uint8 with one bit per element")
-        L.check(lib.edt_outer_step_tail(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
-                                        L.dtype_code(workers[0]), len(workers), L.ptr(momentum),
-                                        int(has_momentum), n, float(lr), float(momentum_coef), int(nesterov),
-                                        L.ptr(tail_bits), L.stream_ptr(theta.device)), "edt_outer_step_tail")
+        L.check(lib.edt_outer_step_tail(*head, L.ptr(tail_bits), L.stream_ptr(theta.device)), "edt_outer_step_tail")
         for b in broadcast or []:          # the broadcast after the step, as diloco._step_flat does
             b.copy_(theta)
         return
     if broadcast:
         if len(workers) <= L.EDT_MAX_WORKERS and len(broadcast) <= L.EDT_MAX_WORKERS:
-            L.check(lib.edt_outer_step_bcast(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
-                                             L.dtype_code(workers[0]), len(workers), L.ptr(momentum),
-                                             int(has_momentum), n, float(lr), float(momentum_coef),
-                                             int(nesterov), L.ptr_array(broadcast), len(broadcast),
+            L.check(lib.edt_outer_step_bcast(*head, L.ptr_array(broadcast), len(broadcast),
                                              L.stream_ptr(theta.device)), "edt_outer_step_bcast")
             return
         outer_step(theta, workers, momentum, has_momentum, lr, momentum_coef, nesterov)
@@ -68,16 +55,10 @@ def outer_step(theta: torch.Tensor, workers: list[torch.Tensor], momentum: torch
             b.copy_(theta)
         return
     if len(workers) <= L.EDT_MAX_WORKERS:
-        L.check(lib.edt_outer_step(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
-                                   L.dtype_code(workers[0]), len(workers), L.ptr(momentum),
-                                   int(has_momentum), n, float(lr), float(momentum_coef),
-                                   int(nesterov), L.stream_ptr(theta.device)), "edt_outer_step")
+        L.check(lib.edt_outer_step(*head, L.stream_ptr(theta.device)), "edt_outer_step")
         return
     ws = torch.empty_like(theta)
-    L.check(lib.edt_outer_step_ws(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
-                                  L.dtype_code(workers[0]), len(workers), L.ptr(momentum),
-                                  int(has_momentum), n, float(lr), float(momentum_coef), int(nesterov),
-                                  L.ptr(ws), L.stream_ptr(theta.device)), "edt_outer_step_ws")
+    L.check(lib.edt_outer_step_ws(*head, L.ptr(ws), L.stream_ptr(theta.device)), "edt_outer_step_ws")
 
 
 def outer_step_scaled(theta: torch.Tensor, workers: list[torch.Tensor], momentum: torch.Tensor | None,
@@ -87,23 +68,11 @@ def outer_step_scaled(theta: torch.Tensor, workers: list[torch.Tensor], momentum
     grad_scale), one fp32 multiply, then the unchanged SGD update. grad_scale: finite, in [0, 1];
     1.0 gives outer_step's bits. At most 64 workers, no fused broadcast (broadcast_theta after it)."""
     lib = L.lib()
-    if not workers:
-        raise L.EdtError("no workers")
-    L.require_device(theta, momentum, *workers)
-    n = theta.numel()
-    if any(w.numel() != n or w.dtype != workers[0].dtype for w in workers):
-        raise L.EdtError("every worker buffer must match theta's size and share one dtype")
+    head = _step_head(theta, workers, momentum, has_momentum, lr, momentum_coef, nesterov)
     if len(workers) > L.EDT_MAX_WORKERS:
         raise L.EdtError(f"the scaled step takes at most {L.EDT_MAX_WORKERS} workers")
-    _check_momentum(momentum, theta)
-    if tail_bits is not None:
-        L.require_device(tail_bits)
-        if tail_bits.dtype != torch.uint8 or tail_bits.numel() * 8 < n:
-            raise L.EdtError("tail_bits: uint8 with one bit per element")
-    L.check(lib.edt_outer_step_scaled(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers),
-                                      L.dtype_code(workers[0]), len(workers), L.ptr(momentum),
-                                      int(has_momentum), n, float(lr), float(momentum_coef), int(nesterov),
-                                      L.ptr(tail_bits), float(grad_scale), L.stream_ptr(theta.device)),
+    _check_tail_bits(tail_bits, theta.numel())
+    L.check(lib.edt_outer_step_scaled(*head, L.ptr(tail_bits), float(grad_scale), L.stream_ptr(theta.device)),
             "edt_outer_step_scaled")
 
 
@@ -126,14 +95,10 @@ def delta_stats(theta: torch.Tensor, workers: list[torch.Tensor], plan: "SlerpPl
         raise L.EdtError("no workers")
     L.require_device(theta, *workers)
     n, K = theta.numel(), len(workers)
-    if any(w.numel() != n or w.dtype != workers[0].dtype for w in workers):
-        raise L.EdtError("every worker buffer must match theta's size and share one dtype")
+    _check_workers(theta, workers)
     if K > L.EDT_MAX_WORKERS:
         raise L.EdtError(f"the statistics pass takes at most {L.EDT_MAX_WORKERS} workers")
-    if plan.relative or plan.seg_offsets[0] != 0 or plan.seg_offsets[-1] != n:
-        raise L.EdtError("the chunk plan must cover theta's elements with absolute starts")
-    if plan.chunks.device != theta.device:
-        raise L.EdtError("the chunk plan lives on another device")
+    _check_stats_plan(plan, n, theta.device, "theta's")
     W = 3 * K + 2
     out = _scratch(theta.device, int(lib.edt_delta_stats_doubles(K, plan.nchunks)))
     L.check(lib.edt_delta_stats(L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers), L.dtype_code(workers[0]),
@@ -229,26 +194,14 @@ def delta_partial(theta: torch.Tensor, workers: list[torch.Tensor], k_total: int
 def sgd_apply(theta: torch.Tensor, acc: torch.Tensor, momentum: torch.Tensor | None,
               has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool) -> None:
     """grad = -round(acc); torch.optim.SGD step on theta (shard) in place."""
-    lib = L.lib()
-    L.require_device(theta, acc, momentum)
-    if acc.dtype != torch.float32 or acc.numel() != theta.numel():
-        raise L.EdtError("acc must be a float32 buffer of theta's size")
-    L.check(lib.edt_sgd_apply(L.ptr(theta), L.dtype_code(theta), L.ptr(acc), L.ptr(momentum),
-                              int(has_momentum), theta.numel(), float(lr), float(momentum_coef),
-                              int(nesterov), L.stream_ptr(theta.device)), "edt_sgd_apply")
+    _sgd_apply("edt_sgd_apply", theta, acc, momentum, has_momentum, lr, momentum_coef, nesterov)
 
 
 def sgd_apply_sum(theta: torch.Tensor, accs: list[torch.Tensor], momentum: torch.Tensor | None,
                   has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool) -> None:
     """grad = -round(((acc_0 + acc_1) + ...)) in that order (fp32), then the SGD step on theta
     (edt_sgd_apply_sum: the reduce_ordered schedule's per-shard step)."""
-    lib = L.lib()
-    L.require_device(theta, momentum, *accs)
-    if not accs or any(a.dtype != torch.float32 or a.numel() != theta.numel() for a in accs):
-        raise L.EdtError("accs: fp32 buffers of theta's size")
-    L.check(lib.edt_sgd_apply_sum(L.ptr(theta), L.dtype_code(theta), L.ptr_array(accs), len(accs), L.ptr(momentum),
-                                  int(has_momentum), theta.numel(), float(lr), float(momentum_coef), int(nesterov),
-                                  L.stream_ptr(theta.device)), "edt_sgd_apply_sum")
+    _sgd_apply_sum("edt_sgd_apply_sum", theta, accs, momentum, has_momentum, lr, momentum_coef, nesterov)
 
 
 def sgd_apply_scaled(theta: torch.Tensor, acc: torch.Tensor, momentum: torch.Tensor | None,
@@ -256,15 +209,8 @@ def sgd_apply_scaled(theta: torch.Tensor, acc: torch.Tensor, momentum: torch.Ten
     """`sgd_apply` with a clipped pseudo-gradient (edt_sgd_apply_scaled): grad = round((-round(acc)) *
     grad_scale), one fp32 multiply, then the unchanged SGD update. grad_scale: finite, in [0, 1];
     1.0 gives sgd_apply's bits."""
-    lib = L.lib()
-    L.require_device(theta, acc, momentum)
-    if acc.dtype != torch.float32 or acc.numel() != theta.numel():
-        raise L.EdtError("acc must be a float32 buffer of theta's size")
-    _check_momentum(momentum, theta)
-    L.check(lib.edt_sgd_apply_scaled(L.ptr(theta), L.dtype_code(theta), L.ptr(acc), L.ptr(momentum),
-                                     int(has_momentum), theta.numel(), float(lr), float(momentum_coef),
-                                     int(nesterov), float(grad_scale), L.stream_ptr(theta.device)),
-            "edt_sgd_apply_scaled")
+    _sgd_apply("edt_sgd_apply_scaled", theta, acc, momentum, has_momentum, lr, momentum_coef, nesterov,
+               float(grad_scale))
 
 
 def sgd_apply_sum_scaled(theta: torch.Tensor, accs: list[torch.Tensor], momentum: torch.Tensor | None,
@@ -272,15 +218,31 @@ def sgd_apply_sum_scaled(theta: torch.Tensor, accs: list[torch.Tensor], momentum
                          grad_scale: float) -> None:
     """`sgd_apply_sum` with a clipped pseudo-gradient (edt_sgd_apply_sum_scaled; sgd_apply_scaled's
     rule on the rank-ordered sum)."""
+    _sgd_apply_sum("edt_sgd_apply_sum_scaled", theta, accs, momentum, has_momentum, lr, momentum_coef, nesterov,
+                   float(grad_scale))
+
+
+# One body per pair: the plain and the scaled wrapper differ in the ABI entry and the trailing grad_scale.
+def _sgd_apply(entry: str, theta, acc, momentum, has_momentum, lr, momentum_coef, nesterov, *grad_scale) -> None:
+    lib = L.lib()
+    L.require_device(theta, acc, momentum)
+    if acc.dtype != torch.float32 or acc.numel() != theta.numel():
+        raise L.EdtError("acc must be a float32 buffer of theta's size")
+    _check_momentum(momentum, theta)
+    L.check(getattr(lib, entry)(L.ptr(theta), L.dtype_code(theta), L.ptr(acc), L.ptr(momentum), int(has_momentum),
+                                theta.numel(), float(lr), float(momentum_coef), int(nesterov), *grad_scale,
+                                L.stream_ptr(theta.device)), entry)
+
+
+def _sgd_apply_sum(entry: str, theta, accs, momentum, has_momentum, lr, momentum_coef, nesterov, *grad_scale) -> None:
     lib = L.lib()
     L.require_device(theta, momentum, *accs)
     if not accs or any(a.dtype != torch.float32 or a.numel() != theta.numel() for a in accs):
         raise L.EdtError("accs: fp32 buffers of theta's size")
     _check_momentum(momentum, theta)
-    L.check(lib.edt_sgd_apply_sum_scaled(L.ptr(theta), L.dtype_code(theta), L.ptr_array(accs), len(accs),
-                                         L.ptr(momentum), int(has_momentum), theta.numel(), float(lr),
-                                         float(momentum_coef), int(nesterov), float(grad_scale),
-                                         L.stream_ptr(theta.device)), "edt_sgd_apply_sum_scaled")
+    L.check(getattr(lib, entry)(L.ptr(theta), L.dtype_code(theta), L.ptr_array(accs), len(accs), L.ptr(momentum),
+                                int(has_momentum), theta.numel(), float(lr), float(momentum_coef), int(nesterov),
+                                *grad_scale, L.stream_ptr(theta.device)), entry)
 
 
 def partial_sum_stats(accs: list[torch.Tensor], gdt_like, plan: "SlerpPlan") -> torch.Tensor:
@@ -300,21 +262,51 @@ def partial_sum_stats(accs: list[torch.Tensor], gdt_like, plan: "SlerpPlan") -> 
         raise L.EdtError("accs: fp32 buffers of one size")
     if len(accs) > L.EDT_MAX_WORKERS:
         raise L.EdtError(f"the statistics pass takes at most {L.EDT_MAX_WORKERS} partials")
-    if plan.relative or plan.seg_offsets[0] != 0 or plan.seg_offsets[-1] != n:
-        raise L.EdtError("the chunk plan must cover the partials' elements with absolute starts")
     dev = accs[0].device
-    if plan.chunks.device != dev:
-        raise L.EdtError("the chunk plan lives on another device")
+    _check_stats_plan(plan, n, dev, "the partials'")
     out = _scratch(dev, int(lib.edt_partial_sum_stats_doubles(plan.nchunks)))
     L.check(lib.edt_partial_sum_stats(L.ptr_array(accs), len(accs), L.dtype_code(gdt_like), n, L.ptr(plan.chunks),
                                       plan.nchunks, L.ptr(out), L.stream_ptr(dev)), "edt_partial_sum_stats")
     return out[:plan.nchunks * 2].view(plan.nchunks, 2)
 
 
-# Argument checks the sharded wrappers share: one message each, whichever wrapper raises it.
+# Argument checks the wrappers share: one message each, whichever wrapper raises it.
+def _check_workers(theta: torch.Tensor, workers) -> None:
+    n = theta.numel()
+    if any(w.numel() != n or w.dtype != workers[0].dtype for w in workers):
+        raise L.EdtError("every worker buffer must match theta's size and share one dtype")
+
+
 def _check_momentum(momentum, theta: torch.Tensor) -> None:
     if momentum is not None and (momentum.numel() != theta.numel() or momentum.dtype != theta.dtype):
         raise L.EdtError("momentum must have theta's size and dtype")
+
+
+def _step_head(theta: torch.Tensor, workers, momentum, has_momentum, lr, momentum_coef, nesterov, *more) -> tuple:
+    """The operand checks of the fused step, plain or scaled (`more`: further device buffers), and
+    the leading arguments every edt_outer_step* entry takes."""
+    if not workers:
+        raise L.EdtError("no workers")
+    L.require_device(theta, momentum, *workers, *more)
+    _check_workers(theta, workers)
+    _check_momentum(momentum, theta)
+    return (L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers), L.dtype_code(workers[0]), len(workers),
+            L.ptr(momentum), int(has_momentum), theta.numel(), float(lr), float(momentum_coef), int(nesterov))
+
+
+def _check_tail_bits(tail_bits, n: int) -> None:
+    if tail_bits is not None:
+        L.require_device(tail_bits)
+        if tail_bits.dtype != torch.uint8 or tail_bits.numel() * 8 < n:
+            raise L.EdtError("tail_bits: uint8 with one bit per element")
+
+
+def _check_stats_plan(plan, n: int, device, what: str) -> None:
+    """A statistics pass's chunk plan over n elements; what: whose elements, for the message."""
+    if plan.relative or plan.seg_offsets[0] != 0 or plan.seg_offsets[-1] != n:
+        raise L.EdtError(f"the chunk plan must cover {what} elements with absolute starts")
+    if plan.chunks.device != device:
+        raise L.EdtError("the chunk plan lives on another device")
 
 
 def _check_residual(residual, n: int) -> None:
@@ -387,9 +379,7 @@ def delta_partial_q(theta: torch.Tensor, workers: list[torch.Tensor], k_total: i
         raise L.EdtError("no workers")
     L.require_device(theta, packed, residual, *workers)
     n = theta.numel()
-    for w in workers:
-        if w.numel() != n or w.dtype != workers[0].dtype:
-            raise L.EdtError("every worker buffer must match theta's size and share one dtype")
+    _check_workers(theta, workers)
     code = _qfmt(fmt)
     _check_packed(packed, n, region_elems, fmt)
     _check_residual(residual, n)
@@ -527,10 +517,7 @@ def pair_merge(b1: torch.Tensor, b2: torch.Tensor | None, m1: torch.Tensor, m2: 
     if any(t is not None and t.dtype != out.dtype for t in (momentum, momentum_in)):
         raise L.EdtError("momentum buffers must have out's dtype")
     mom_in = momentum if momentum_in is None else momentum_in
-    if tail_bits is not None:
-        L.require_device(tail_bits)
-        if tail_bits.dtype != torch.uint8 or tail_bits.numel() * 8 < n:
-            raise L.EdtError("tail_bits: uint8 with one bit per element")
+    _check_tail_bits(tail_bits, n)
     L.check(lib.edt_pair_merge_tail(L.ptr(b1), L.ptr(b2), L.ptr(m1), L.ptr(m2), L.dtype_code(m1),
                                     L.ptr(out), L.dtype_code(out), L.ptr(mom_in), L.ptr(momentum),
                                     int(has_momentum), n, float(lr), float(momentum_coef), int(nesterov),
@@ -651,7 +638,6 @@ class SlerpPlan:
         """numpy int64 [nseg]: the segments' sizes (cached)."""
         got = self.__dict__.get("_seg_numel")
         if got is None:
-            import numpy as np
             got = self.__dict__["_seg_numel"] = np.diff(np.asarray(self.seg_offsets, dtype=np.int64))
         return got
 
@@ -670,7 +656,6 @@ def make_slerp_plan(seg_offsets: list[int], device: torch.device,
     got = lib.edt_slerp_make_chunks(offs, nseg, chunk_elems, desc, nchunks, first)
     if got != nchunks:
         L.check(-1, "edt_slerp_make_chunks")
-    import numpy as np
     host = np.ctypeslib.as_array(desc).astype(np.int64)[:3 * nchunks].copy().reshape(-1, 3)
     if relative and nchunks:
         host[:, 0] -= np.asarray(seg_offsets, dtype=np.int64)[host[:, 2]]
@@ -700,7 +685,6 @@ def host_dispatch() -> dict:
     "<internal api> <version> <architecture>" (threadpoolctl; None when not importable)."""
     global _HOST_DISPATCH
     if _HOST_DISPATCH is None:
-        import numpy as np
         disp = {}
         try:                                    # numpy >= 2.0 only
             from numpy.lib import introspect
@@ -792,7 +776,6 @@ def reference_coefficients(dots, t, dot_threshold: float = 0.9995):
     (1 - t, t). numpy's float32 arccos / sin are the reference's own dependency (SVML / numpy's SIMD
     loops on an AVX-512 host): no device restatement of them is bit-exact. dots: float32 [..., nseg];
     t: float64 [nseg]. Returns float32 [..., nseg, 2]."""
-    import numpy as np
     d = np.asarray(dots, dtype=np.float32)
     tt = np.broadcast_to(np.asarray(t, dtype=np.float64), d.shape)
     tf = tt.astype(np.float32)
@@ -849,7 +832,6 @@ def _reference_finish(dots: torch.Tensor, flag: torch.Tensor, val: torch.Tensor,
     coefficients a pass already blended with (`coef_used`, [.., nseg, 2]) — the segments whose
     coefficients changed. dots / flag / val: [..., nseg] device tensors. Returns (dots, coef,
     changed) as device tensors shaped like the inputs (changed: int32 or None)."""
-    import numpy as np
     shp = dots.shape
     d = dots.reshape(-1, dots.shape[-1])[:, :nseg].cpu().numpy()
     f = flag.reshape(-1, flag.shape[-1])[:, :nseg].cpu().numpy()
@@ -910,7 +892,6 @@ def _speculation_pays(plan: SlerpPlan, in_bytes: int, out_bytes: int, wait: bool
     back to back — the previous decision stands, so deciding never synchronises the device."""
     if getattr(plan, "_last_thr", None) is None:
         return True
-    import numpy as np
     dots = _host_dots(plan, "_dots", wait)
     if dots is None:
         return getattr(plan, "_last_speculate", True)
@@ -1035,7 +1016,6 @@ def writes_safe(starts, nbytes) -> bool:
     either form. Identical spans are grouped; a group holding an output may hold only spans of that
     output's own segment; distinct groups that overlap are unsafe when either holds an output (a
     sorted sweep: running furthest end of every group / of the groups holding an output)."""
-    import numpy as np
     st = np.asarray(starts, dtype=np.int64)
     nb = np.asarray(nbytes, dtype=np.int64)
     nseg = st.size // 3
@@ -1116,7 +1096,6 @@ class SlerpListBinding:
         """checked=True (merge.slerp_tensors): the caller has verified devices, contiguity, sizes
         against the plan and the two dtypes; the per-tensor Python pass is skipped (alignment and
         the overlap rule are checked in C either way)."""
-        import numpy as np
         lib = L.lib()
         T = len(v0s)
         if not plan.relative or T != plan.nseg or len(v1s) != T or len(outs) != T:
@@ -1164,7 +1143,6 @@ class SlerpListBinding:
         return self
 
     def _bind(self, plan, p0, p1, po, in_dt, out_dt, keep):
-        import numpy as np
         lib, T = L.load_library(), plan.nseg       # host validation only; merge() insists on the device
         self.plan, self.in_dt, self.out_dt = plan, L.dtype_code(in_dt), L.dtype_code(out_dt)
         self.in_size, self.out_size = _ELEM_SIZE[in_dt], _ELEM_SIZE[out_dt]
@@ -1191,7 +1169,6 @@ class SlerpListBinding:
         with their memory held; the outputs are views of a fresh buffer at 16-byte aligned offsets,
         apart from every parent by construction). The table image is written without the C checks
         (every invariant they test holds by construction), into the plan's pinned staging buffer."""
-        import numpy as np
         self = cls.__new__(cls)
         T = plan.nseg
         if not plan.relative or not (len(p0) == len(p1) == len(pout) == T):
@@ -1351,7 +1328,6 @@ def slerp_population(plan: SlerpPlan, members: list[torch.Tensor], pairs, outs: 
         elif d is None or d.shape[0] == 0:        # previous dots still in flight: keep its decision
             speculate = getattr(plan, "_last_pop_speculate", True)
         else:
-            import numpy as np
             sizes = np.diff(np.asarray(plan.seg_offsets, dtype=np.int64))
             f = float((sizes[None, :] * (np.abs(d) <= plan._last_thr)).sum()) / max(1, int(sizes.sum()) * d.shape[0])
             # member-major passes over D distinct parents: speculating costs (1 + f)(D b_in + Q b_out)

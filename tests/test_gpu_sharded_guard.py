@@ -172,6 +172,23 @@ def test_scaled_sgd_refuses_a_bad_scale(dev):
     assert torch.equal(bits(t.cpu()), bits(theta)) and not m.any()
 
 
+def test_plain_sgd_refuses_a_wrong_dtype_momentum(dev):
+    """The plain entries check the momentum as the scaled ones do: a bf16 momentum under an fp32
+    theta is refused before anything is launched (the kernel would reinterpret its bytes)."""
+    from evolutionarydistributedtraining_amd._lib import EdtError
+    ops = _ops()
+    n = 64
+    theta, gens = _sgd_case(n, 2, F32, seed=11)
+    t, m = theta.to(dev), torch.zeros(n, dtype=BF16, device=dev)
+    ps = [p.to(dev) for p in gens[0]]
+    with pytest.raises(EdtError, match="momentum must have theta's size and dtype"):
+        ops.sgd_apply(t, ps[0], m, False, LR, 0.9, NEST)
+    with pytest.raises(EdtError, match="momentum must have theta's size and dtype"):
+        ops.sgd_apply_sum(t, ps, m, False, LR, 0.9, NEST)
+    torch.cuda.synchronize()
+    assert torch.equal(bits(t.cpu()), bits(theta)) and not m.any()
+
+
 # ---- ShardedOuterSync(guard=...) on virtual ranks -----------------------------------------------
 
 def _guard(**kw):
