@@ -53,6 +53,10 @@ struct TensorArgs {
     uint64_t t;
     __device__ __forceinline__ const void* wp(int k) const { return w[(uint64_t)k * T + t]; }
 };
+// the scaled list step's tensor (SC): the clip coefficient beside the same fields
+struct TensorArgsScaled : TensorArgs {
+    float grad_scale;
+};
 
 // MODE_CHAIN = MODE_FUSED for populations above EDT_MAX_WORKERS: launches of <= 64 workers
 // carry the running sum in theta's dtype (lossless: it is rounded to that dtype after every add).
@@ -162,9 +166,14 @@ struct ListArgs {
     const uint8_t* tail;        // nullable: bf16 scalar-tail bits, tensor t's from byte tail_off[t]
     const uint64_t* tail_off;   // T
 };
+// edt_outer_step_list_scaled's block (SC): grad_scale trails, so the unscaled kernels keep theirs
+struct ListArgsScaled : ListArgs {
+    float grad_scale;
+};
 
-template <int GDT, int WDT, int KC, int DIV>
-__device__ __forceinline__ void outer_list_chunk(const ListArgs& L, const uint64_t* prefix, uint64_t b) {
+// SC: grad = round_g(-acc * L.grad_scale) (edt_outer_step_list_scaled), outer_elems' SC branch.
+template <int GDT, int WDT, int KC, int DIV, bool SC, class LA>
+__device__ __forceinline__ void outer_list_chunk(const LA& L, const uint64_t* prefix, uint64_t b) {
     uint64_t lo = 0, hi = L.T;                       // last t with prefix[t] <= b
     while (hi - lo > 1) {
         const uint64_t mid = (lo + hi) >> 1;
@@ -176,7 +185,9 @@ __device__ __forceinline__ void outer_list_chunk(const ListArgs& L, const uint64
     const uint64_t n = nf & ~kVecFlag;
     const uint64_t c0 = (b - prefix[t]) * kListChunk;
     const uint64_t c1 = c0 + kListChunk < n ? c0 + kListChunk : n;
-    TensorArgs a;
+    using TA = std::conditional_t<SC, TensorArgsScaled, TensorArgs>;
+    TA a;
+    if constexpr (SC) a.grad_scale = L.grad_scale;
     a.theta = L.theta[t];
     a.mom = L.sgd.use_momentum ? L.mom[t] : nullptr;
     a.acc_out = nullptr;
@@ -197,26 +208,26 @@ __device__ __forceinline__ void outer_list_chunk(const ListArgs& L, const uint64
         constexpr uint64_t tile = (uint64_t)kBlock * kVec;
         const uint64_t vend = c0 + (c1 - c0) / tile * tile;
         for (uint64_t i = c0 + 4ull * threadIdx.x; i < vend; i += tile)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec, TensorArgs, 4 * kBlock>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec, TA, 4 * kBlock, false, SC>(a, i);
         for (uint64_t i = vend + threadIdx.x; i < c1; i += kBlock)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC>(a, i);
     } else if (nf & kVecFlag) {
         const uint64_t vend = c0 + (c1 - c0) / kVec * kVec;
         for (uint64_t i = c0 + (uint64_t)threadIdx.x * kVec; i < vend; i += (uint64_t)kBlock * kVec)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec, TA, 4, false, SC>(a, i);
         const uint64_t i = vend + threadIdx.x;
-        if (i < c1) outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1>(a, i);
+        if (i < c1) outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC>(a, i);
     } else {
         for (uint64_t i = c0 + threadIdx.x; i < c1; i += kBlock)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC>(a, i);
     }
 }
 
 // LDS = true: the chunk prefix sums are staged in LDS once per workgroup (dynamic shared
 // memory, (T + 1) x 8 bytes), so the per-chunk tensor search costs LDS reads, not a chain of
 // dependent global loads; LDS = false (very long tensor lists) searches the global table.
-template <int GDT, int WDT, int KC, int DIV, bool LDS>
-__global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_list_kernel(ListArgs L) {
+template <int GDT, int WDT, int KC, int DIV, bool LDS, bool SC = false>
+__global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_list_kernel(std::conditional_t<SC, ListArgsScaled, ListArgs> L) {
     extern __shared__ uint64_t s_prefix[];
     const uint64_t* prefix = L.prefix;
     if constexpr (LDS) {
@@ -224,7 +235,7 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_list_kernel(ListA
         __syncthreads();
         prefix = s_prefix;
     }
-    for (uint64_t b = blockIdx.x; b < L.chunks; b += gridDim.x) outer_list_chunk<GDT, WDT, KC, DIV>(L, prefix, b);
+    for (uint64_t b = blockIdx.x; b < L.chunks; b += gridDim.x) outer_list_chunk<GDT, WDT, KC, DIV, SC>(L, prefix, b);
 }
 
 // SGD from N per-rank fp32 partial sums of the same shard, summed in rank order (the sharded
@@ -344,14 +355,15 @@ int launch_outer(int gdt, int wdt, const OuterArgs& a, bool vec, hipStream_t s) 
 
 constexpr uint64_t kListLdsMaxTensors = 8191;          // (T + 1) x 8 B <= 64 KiB of LDS
 
-int launch_list(int gdt, int wdt, const ListArgs& L, bool div_exact, unsigned grid, hipStream_t s) {
+template <bool SC, class LA>
+int launch_list(int gdt, int wdt, const LA& L, bool div_exact, unsigned grid, hipStream_t s) {
     const bool lds = L.T <= kListLdsMaxTensors;
     const size_t shm = lds ? (size_t)(L.T + 1) * sizeof(uint64_t) : 0;
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_kc_div<KC_FUSED>(L.K, div_exact, [&](auto KC, auto DIV) {
             return with_bool(lds, [&](auto LDS) {
                 outer_list_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value, decltype(DIV)::value,
-                                  decltype(LDS)::value><<<grid, kBlock, shm, s>>>(L);
+                                  decltype(LDS)::value, SC><<<grid, kBlock, shm, s>>>(L);
                 return check_launch("outer_list_kernel");
             });
         });
@@ -564,12 +576,17 @@ uint64_t edt_outer_list_workspace_bytes(int T, int K) {
 
 }   // extern "C"
 
+// SC: the scaled entry (grad_scale checked first, so a refused call writes nothing).
+template <bool SC>
 static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
                                 void* const* momentum_t, int has_momentum, const uint64_t* numel, int T,
                                 double lr, double momentum_coef, int nesterov, const uint8_t* tail,
-                                const uint64_t* tail_off, void* workspace, uint64_t workspace_bytes, void* stream) {
+                                const uint64_t* tail_off, float grad_scale, void* workspace, uint64_t workspace_bytes,
+                                void* stream) {
     g_err[0] = 0;
     if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
+    if constexpr (SC)
+        if (int rc = check_grad_scale(grad_scale)) return rc;
     if (K < 1 || K > EDT_MAX_WORKERS)
         return fail(EDT_ERR_ARG, "worker count %d out of range [1, %d]", K, EDT_MAX_WORKERS);
     if (T < 0) return fail(EDT_ERR_ARG, "tensor count %d < 0", T);
@@ -626,7 +643,8 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     hipError_t e = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "tensor table upload failed: %s", hipGetErrorString(e));
     const uint64_t* d = static_cast<const uint64_t*>(workspace);
-    ListArgs L;
+    std::conditional_t<SC, ListArgsScaled, ListArgs> L;
+    if constexpr (SC) L.grad_scale = grad_scale;
     L.prefix = d;
     L.numel = d + T + 1;
     L.theta = reinterpret_cast<void* const*>(d + 2 * (uint64_t)T + 1);
@@ -641,7 +659,7 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     L.tail = tail;
     L.tail_off = d + 4 * (uint64_t)T + 1 + (uint64_t)K * T;
     const unsigned grid = chunks > kMaxBlocks ? (unsigned)kMaxBlocks : (unsigned)chunks;   // grid-stride
-    return launch_list(gdt, wdt, L, !is_pow2(K), grid, st);
+    return launch_list<SC>(gdt, wdt, L, !is_pow2(K), grid, st);
 }
 
 // The two sharded SGD entries and their scaled forms (SC: the clip coefficient is checked first,
@@ -709,8 +727,8 @@ int edt_outer_step_list(void* const* theta_t, int gdt, const void* const* theta_
                         void* const* momentum_t, int has_momentum, const uint64_t* numel, int T,
                         double lr, double momentum_coef, int nesterov, void* workspace,
                         uint64_t workspace_bytes, void* stream) {
-    return outer_step_list_impl(theta_t, gdt, theta_k, wdt, K, momentum_t, has_momentum, numel, T, lr,
-                                momentum_coef, nesterov, nullptr, nullptr, workspace, workspace_bytes, stream);
+    return outer_step_list_impl<false>(theta_t, gdt, theta_k, wdt, K, momentum_t, has_momentum, numel, T, lr,
+                                       momentum_coef, nesterov, nullptr, nullptr, 1.f, workspace, workspace_bytes, stream);
 }
 
 int edt_outer_step_list_tail(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
@@ -718,9 +736,19 @@ int edt_outer_step_list_tail(void* const* theta_t, int gdt, const void* const* t
                              double lr, double momentum_coef, int nesterov, const uint8_t* tail_bits,
                              const uint64_t* tail_byte_offset, void* workspace, uint64_t workspace_bytes,
                              void* stream) {
-    return outer_step_list_impl(theta_t, gdt, theta_k, wdt, K, momentum_t, has_momentum, numel, T, lr,
-                                momentum_coef, nesterov, tail_bits, tail_byte_offset, workspace, workspace_bytes,
-                                stream);
+    return outer_step_list_impl<false>(theta_t, gdt, theta_k, wdt, K, momentum_t, has_momentum, numel, T, lr,
+                                       momentum_coef, nesterov, tail_bits, tail_byte_offset, 1.f, workspace,
+                                       workspace_bytes, stream);
+}
+
+int edt_outer_step_list_scaled(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
+                               void* const* momentum_t, int has_momentum, const uint64_t* numel, int T,
+                               double lr, double momentum_coef, int nesterov, const uint8_t* tail_bits,
+                               const uint64_t* tail_byte_offset, float grad_scale, void* workspace,
+                               uint64_t workspace_bytes, void* stream) {
+    return outer_step_list_impl<true>(theta_t, gdt, theta_k, wdt, K, momentum_t, has_momentum, numel, T, lr,
+                                      momentum_coef, nesterov, tail_bits, tail_byte_offset, grad_scale, workspace,
+                                      workspace_bytes, stream);
 }
 
 int edt_delta_partial(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,

@@ -2,6 +2,8 @@
 // read-only pass over theta and the K worker arenas that forms, per chunk of the arena, the fp64
 // sums of the very deltas and mean the fused step (edt_outer.hip) would apply to these operands,
 // and counts what is not finite — so a caller can screen workers and clip before theta is touched.
+// edt_delta_stats_list is the same pass over T separate tensors (a device table of their pointers,
+// chunk starts relative to their tensor): one kernel body, two operand accessors.
 // The per-element arithmetic is edt_step.h's (delta_of, mean_add: add_delta's two halves), the
 // sums' order edt_chunksum.h's (the canonical chunk-sum order).
 #include "edt_chunksum.h"
@@ -34,7 +36,43 @@ struct StatsArgs {
     float kdiv;
     float kinv;
     StatsWorkers w;
+    static constexpr bool kList = false;
+    __device__ __forceinline__ const StatsArgs& operands(uint64_t) const { return *this; }
+    __device__ __forceinline__ const void* th() const { return theta; }
+    __device__ __forceinline__ const void* wp(int k) const { return w.p[k]; }
 };
+
+// The tensor-list form's arguments (edt_delta_stats_list): the operands are T separate tensors
+// named by a device table, and a chunk's start is relative to its tensor chunks[3 c + 2].
+struct StatsListArgs;
+// The operand accessor: where chunk c's operands lie (th, wp(k)). The arena form's are the launch's
+// own pointers (StatsArgs is its own accessor), the list form's those of the chunk's tensor t, read
+// from the device table (uniform across the workgroup).
+struct TensorOperands {
+    const StatsListArgs& a;
+    uint64_t t;
+    __device__ __forceinline__ const void* th() const;
+    __device__ __forceinline__ const void* wp(int k) const;
+};
+
+struct StatsListArgs {
+    const void* const* theta;   // T
+    const void* const* w;       // K * T, worker-major
+    const uint64_t* vec;        // T: nonzero when the tensor's K + 1 pointers are all 16-byte aligned
+    const uint64_t* chunks;
+    double* rows;
+    uint64_t units;
+    uint64_t u0;
+    uint64_t T;
+    int K;
+    float kdiv;
+    float kinv;
+    static constexpr bool kList = true;
+    __device__ __forceinline__ TensorOperands operands(uint64_t c) const { return {*this, chunks[3 * c + 2]}; }
+};
+__device__ __forceinline__ const void* TensorOperands::th() const { return a.theta[t]; }
+__device__ __forceinline__ const void* TensorOperands::wp(int k) const { return a.w[(uint64_t)k * a.T + t]; }
+
 
 template <int DT, bool VEC, bool NT>
 __device__ __forceinline__ void ld8(const void* p, uint64_t i, float (&x)[kVec]) {
@@ -74,11 +112,18 @@ __device__ __forceinline__ void dot_chain(const float (&x)[N], const float (&y)[
 // edge element computes on zeros: every delta is then +0, finite, and adds nothing. The four tile
 // sums are combined through LDS as the tree does, (t0 + t1) + (t2 + t3): a level-2 row per unit.
 // KM: K <= kStatsGroup, the S_km columns are formed; else they are written as 0.
-template <int GDT, int WDT, int DIV, int KC, bool KM, bool VEC>
-__global__ __launch_bounds__(kBlock) void delta_stats_kernel(StatsArgs a) {
+// Args = StatsArgs: the arena form, indices are the arena's, VEC the launch's alignment.
+// Args = StatsListArgs: the chunk row names its tensor and indices are inside it (its aligned body
+// starts at its element 0, so it has a tail only); a launch takes the tensors whose alignment is
+// its VEC and leaves the others' units to the other launch (the whole workgroup: uniform).
+template <int GDT, int WDT, int DIV, int KC, bool KM, bool VEC, class Args>
+__global__ __launch_bounds__(kBlock) void delta_stats_kernel(Args a) {
     __shared__ double part[kWavesPerBlock][kStatsMaxWidth];
     const uint64_t u = a.u0 + blockIdx.x;
     if (u >= a.units) return;                         // the whole workgroup
+    const auto& o = a.operands(u / kStatsUpc);       // a itself (no copy), or the chunk's tensor
+    if constexpr (Args::kList)
+        if ((a.vec[o.t] != 0) != VEC) return;
     constexpr bool NT = nt_worker_loads<WDT, 4>();
     constexpr int G = kStatsGroup;
     const int K = KC > 0 ? KC : a.K;
@@ -98,8 +143,8 @@ __global__ __launch_bounds__(kBlock) void delta_stats_kernel(StatsArgs a) {
         });
 
     float g[kVec] = {}, ge[1] = {}, acc[kVec] = {}, acce[1] = {};
-    if (has_vec) ld8<GDT, VEC, false>(a.theta, i, g);
-    if (has_edge) ld<GDT, 1>(a.theta, e, ge);
+    if (has_vec) ld8<GDT, VEC, false>(o.th(), i, g);
+    if (has_edge) ld<GDT, 1>(o.th(), e, ge);
     double smm = 0.0, cm = 0.0, skm[G] = {};
     double* row = &part[wave][0];
 
@@ -112,8 +157,8 @@ __global__ __launch_bounds__(kBlock) void delta_stats_kernel(StatsArgs a) {
             for (int j = 0; j < kVec; ++j) d[q][j] = 0.f;
             de[q][0] = 0.f;
             if (KC > 0 ? q < KC : k0 + q < K) {
-                if (has_vec) ld8<WDT, VEC, NT>(a.w.p[k0 + q], i, d[q]);
-                if (has_edge) ld<WDT, 1>(a.w.p[k0 + q], e, de[q]);
+                if (has_vec) ld8<WDT, VEC, NT>(o.wp(k0 + q), i, d[q]);
+                if (has_edge) ld<WDT, 1>(o.wp(k0 + q), e, de[q]);
             }
         }
 #pragma unroll
@@ -190,15 +235,42 @@ __global__ __launch_bounds__(kBlock) void delta_stats_kernel(StatsArgs a) {
     }
 }
 
-template <int GDT, int WDT, int DIV, int KC, bool KM, bool VEC>
-int launch_stats(StatsArgs a, hipStream_t s) {
+template <int GDT, int WDT, int DIV, int KC, bool KM, bool VEC, class A>
+int launch_stats(A a, hipStream_t s) {
     const uint64_t units = a.units;
     for (uint64_t u0 = 0; u0 < units; u0 += kUnitGridCap) {
         a.u0 = u0;
-        delta_stats_kernel<GDT, WDT, DIV, KC, KM, VEC><<<unit_grid(units - u0), kBlock, 0, s>>>(a);
+        delta_stats_kernel<GDT, WDT, DIV, KC, KM, VEC, A><<<unit_grid(units - u0), kBlock, 0, s>>>(a);
         if (int rc = check_launch("delta_stats_kernel")) return rc;
     }
     return EDT_OK;
+}
+
+// The K = 8 and DIV / KM dispatch of both forms, then the tree over the rows. LIST: the alignment
+// is per tensor — the vector launch, then (vec false: some tensor is unaligned) the scalar one.
+template <class A, bool LIST>
+int dispatch_stats(const A& a, Bool<LIST>, int gdt, int wdt, bool vec, int64_t nchunks, double* out, hipStream_t s) {
+    const int K = a.K;
+    const bool km = K <= kStatsGroup;
+    int rc = with_pair(gdt, wdt, [&](auto G, auto Wd) {
+        constexpr int GD = decltype(G)::value, WD = decltype(Wd)::value;
+        auto go = [&](auto V) {
+            constexpr bool VEC = decltype(V)::value;
+            if (K == 8) return launch_stats<GD, WD, 0, 8, true, VEC>(a, s);
+            return with_bool(!is_pow2(K), [&](auto D) {
+                constexpr int DIV = decltype(D)::value ? 1 : 0;
+                return with_bool(km, [&](auto M) { return launch_stats<GD, WD, DIV, 0, decltype(M)::value, VEC>(a, s); });
+            });
+        };
+        if constexpr (LIST) {                         // vec: some tensor is off a 16-byte boundary
+            if (int r = go(Bool<true>{})) return r;
+            return vec ? EDT_OK : go(Bool<false>{});
+        } else {
+            return with_bool(vec, go);
+        }
+    });
+    if (rc) return rc;
+    return launch_tree_reduce(a.rows, stats_width(K), kStatsUpc, kStatsUpc, 1, nchunks, out, s);
 }
 
 // ---- the mean pseudo-gradient of a sharded step, from the per-rank partials its owner holds ------
@@ -365,21 +437,72 @@ int edt_delta_stats(const void* theta_g, int gdt, const void* const* theta_k, in
     a.K = K;
     a.kdiv = (float)K;
     a.kinv = 1.0f / (float)K;
+    return dispatch_stats(a, Bool<false>{}, gdt, wdt, vec, nchunks, out, (hipStream_t)stream);
+}
+
+uint64_t edt_delta_stats_list_workspace_bytes(int T, int K) {
+    if (T < 0 || K < 1 || K > EDT_MAX_WORKERS) return 0;
+    // table: theta[T] | w[K*T] | vec[T]   (all 8-byte words)
+    return ((uint64_t)K + 2) * (uint64_t)T * sizeof(uint64_t);
+}
+
+int edt_delta_stats_list(const void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
+                         const uint64_t* numel, int T, const uint64_t* chunk_desc, int64_t nchunks, double* out,
+                         void* workspace, uint64_t workspace_bytes, void* stream) {
+    g_err[0] = 0;
+    if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
+    if (K < 1 || K > EDT_MAX_WORKERS)
+        return fail(EDT_ERR_ARG, "worker count %d out of range [1, %d]", K, EDT_MAX_WORKERS);
+    if (T < 0) return fail(EDT_ERR_ARG, "tensor count %d < 0", T);
+    if (nchunks < 0) return fail(EDT_ERR_ARG, "negative chunk count");
+    if (T == 0 || nchunks == 0) return EDT_OK;
+    if (!theta_t || !theta_k || !numel) return fail(EDT_ERR_ARG, "null tensor table");
+    if (!chunk_desc || !out) return fail(EDT_ERR_ARG, "null chunk table or output");
+    if (reinterpret_cast<uintptr_t>(out) & 7u) return fail(EDT_ERR_ARG, "out must be 8-byte aligned");
+    const uint64_t need = edt_delta_stats_list_workspace_bytes(T, K);
+    if (!workspace || workspace_bytes < need)
+        return fail(EDT_ERR_ARG, "workspace of %llu bytes needed", (unsigned long long)need);
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(EDT_ERR_ARG, "workspace must be 8-byte aligned");
+    thread_local std::vector<uint64_t> h;
+    h.assign(need / sizeof(uint64_t), 0);
+    uint64_t* pth = h.data();
+    uint64_t* pw = pth + T;
+    uint64_t* pvec = pw + (uint64_t)K * T;
+    bool all_vec = true;
+    for (int t = 0; t < T; ++t) {
+        bool vec = true;
+        if (numel[t]) {                               // an empty tensor has no chunks: never read
+            if (!theta_t[t]) return fail(EDT_ERR_ARG, "theta_t[%d] is null", t);
+            vec = aligned16(theta_t[t]);
+            for (int k = 0; k < K; ++k) {
+                const void* p = theta_k[(uint64_t)k * T + t];
+                if (!p) return fail(EDT_ERR_ARG, "theta_k[%d][%d] is null", k, t);
+                vec = vec && aligned16(p);
+            }
+        }
+        pth[t] = reinterpret_cast<uintptr_t>(theta_t[t]);
+        for (int k = 0; k < K; ++k) pw[(uint64_t)k * T + t] = reinterpret_cast<uintptr_t>(theta_k[(uint64_t)k * T + t]);
+        pvec[t] = vec ? 1 : 0;
+        all_vec = all_vec && vec;
+    }
     hipStream_t s = (hipStream_t)stream;
-    const bool km = K <= kStatsGroup;
-    int rc = with_pair(gdt, wdt, [&](auto G, auto Wd) {
-        constexpr int GD = decltype(G)::value, WD = decltype(Wd)::value;
-        return with_bool(vec, [&](auto V) {
-            constexpr bool VEC = decltype(V)::value;
-            if (K == 8) return launch_stats<GD, WD, 0, 8, true, VEC>(a, s);
-            return with_bool(!is_pow2(K), [&](auto D) {
-                constexpr int DIV = decltype(D)::value ? 1 : 0;
-                return with_bool(km, [&](auto M) { return launch_stats<GD, WD, DIV, 0, decltype(M)::value, VEC>(a, s); });
-            });
-        });
-    });
-    if (rc) return rc;
-    return launch_tree_reduce(a.rows, stats_width(K), kStatsUpc, kStatsUpc, 1, nchunks, out, s);
+    // pageable source, overwritten by this thread's next call: stream-ordered, as edt_outer_step_list's
+    hipError_t e = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "tensor table upload failed: %s", hipGetErrorString(e));
+    const uint64_t* d = static_cast<const uint64_t*>(workspace);
+    StatsListArgs a;
+    memset(&a, 0, sizeof(a));
+    a.theta = reinterpret_cast<const void* const*>(d);
+    a.w = reinterpret_cast<const void* const*>(d + T);
+    a.vec = d + (uint64_t)T + (uint64_t)K * T;
+    a.T = (uint64_t)T;
+    a.chunks = chunk_desc;
+    a.rows = out + (uint64_t)nchunks * stats_width(K);
+    a.units = (uint64_t)nchunks * kStatsUpc;
+    a.K = K;
+    a.kdiv = (float)K;
+    a.kinv = 1.0f / (float)K;
+    return dispatch_stats(a, Bool<true>{}, gdt, wdt, all_vec, nchunks, out, s);
 }
 
 }  // extern "C"

@@ -132,19 +132,53 @@ def _measure(theta, workers, plan, per_tensor: bool) -> dict:
     return stats_totals(rows, len(workers), first)
 
 
+def _stats_list_plan(state, thetas):
+    """The relative chunk plan of the tensor-list statistics pass (segment t = tensor t), kept on
+    the state, keyed by the sizes and the device like `_stats_plan`."""
+    offs = [0]
+    for t in thetas:
+        offs.append(offs[-1] + t.numel())
+    key = (tuple(offs), str(thetas[0].device))
+    cached = getattr(state, "_stats_list_plan", None)
+    if cached is None or cached[0] != key:
+        cached = state._stats_list_plan = (key, ops.make_slerp_plan(offs, thetas[0].device, relative=True))
+    return cached[1]
+
+
+def _measure_list(thetas, workers, plan, per_tensor: bool) -> dict:
+    rows = ops.delta_stats_list(thetas, workers, plan).cpu().numpy()    # the step's one host sync
+    first = plan.seg_first.cpu().numpy() if per_tensor else None
+    return stats_totals(rows, len(workers), first)
+
+
 def _guard_pass(theta, workers, state, guard: OuterGuard, numels):
-    """Runs the statistics, decides, and records state.last_stats. Returns (survivor indices,
-    clip_coef). Raises before anything is written."""
-    K = len(workers)
-    if K > L_MAX:
+    """The guard over flat arenas: (survivor indices, clip_coef), state.last_stats recorded. Raises
+    before anything is written."""
+    if len(workers) > L_MAX:
         raise EdtError(f"a guarded step takes at most {L_MAX} workers")
     plan = _stats_plan(state, theta, numels if guard.per_tensor else None)
-    first = _measure(theta, workers, plan, guard.per_tensor)
+    return _guard_decide(lambda ws: _measure(theta, ws, plan, guard.per_tensor), workers, state, guard)
+
+
+def _guard_pass_list(thetas, workers, state, guard: OuterGuard):
+    """The guard over separate tensors, read where they lie (`ops.delta_stats_list`): the segments
+    are the tensors, so per_tensor needs no second plan."""
+    if len(workers) > L_MAX:
+        raise EdtError(f"a guarded step takes at most {L_MAX} workers")
+    plan = _stats_list_plan(state, thetas)
+    return _guard_decide(lambda ws: _measure_list(thetas, ws, plan, guard.per_tensor), workers, state, guard)
+
+
+def _guard_decide(measure, workers, state, guard: OuterGuard):
+    """Runs the statistics (measure(workers) -> totals), decides, and records state.last_stats.
+    Returns (survivor indices, clip_coef). Raises before anything is written."""
+    K = len(workers)
+    first = measure(workers)
     rep = state.last_stats = dict(report(first), clip_coef=None, dropped=[])
     survivors, clip = guard_decision(first, guard)
     final = first
     if clip is None:                            # workers dropped: the norm of what is applied
-        final = _measure(theta, [workers[k] for k in survivors], plan, guard.per_tensor)
+        final = measure([workers[k] for k in survivors])
         rep["dropped"] = [k for k in range(K) if k not in survivors]
         fold_remeasured(rep, report(final), survivors, K)
         _, clip = guard_decision(final, guard)
@@ -214,8 +248,12 @@ def _step_flat(theta: torch.Tensor, workers: list[torch.Tensor], state: OuterSta
 
 
 def _step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]], state: OuterState,
-               lr: float, momentum: float, nesterov: bool, tails=None) -> None:
+               lr: float, momentum: float, nesterov: bool, tails=None, guard: OuterGuard | None = None) -> None:
     check_sgd_hparams(lr, momentum, nesterov)
+    clip = 1.0
+    if guard is not None:                       # before anything is created or written
+        survivors, clip = _guard_pass_list(thetas, workers, state, guard)
+        workers = [workers[k] for k in survivors]
     state.hparams = dict(lr=lr, momentum=momentum, nesterov=nesterov)
     moms = None
     if momentum != 0:
@@ -227,8 +265,11 @@ def _step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]], st
         else:
             moms = ParamLayout.of(thetas).views(flat)
             state._list_views = (flat, shapes, moms)
-    ops.outer_step_list(thetas, workers, moms, state.has_momentum if momentum != 0 else False,
-                        lr, momentum, nesterov, tails=tails)
+    has = state.has_momentum if momentum != 0 else False
+    if clip != 1.0:
+        ops.outer_step_list_scaled(thetas, workers, moms, has, lr, momentum, nesterov, clip, tails=tails)
+    else:
+        ops.outer_step_list(thetas, workers, moms, has, lr, momentum, nesterov, tails=tails)
     if momentum != 0:
         state.has_momentum = True
     state.steps += 1
@@ -245,15 +286,17 @@ def outer_step(base_params, worker_params, state: OuterState | None = None, lr: 
     state:         the carried outer-optimiser state (None on the first generation).
     One launch either way: over the flat arenas when each list is a run of views of one arena
     (`params.arena_of_module`), else over the tensor lists themselves (`ops.outer_step_list`,
-    no packing). Only populations above 64 workers with separate tensors are packed first.
+    no packing). Only unguarded populations above 64 workers with separate tensors are packed first.
     cpu_tails = (Vec::size(), torch threads) of the reference's master, e.g. (32, 8): bf16 results
     bit-exact with the reference run there, torch's scalar tails included (torchcompat; r5: the
     tensor-list form reads per-tensor masks, edt_outer_step_list_tail, so nothing is packed; the
     masks are kept on `state` across generations).
     guard: an OuterGuard — the pseudo-gradient is measured, screened and clipped before the step
-    (state.last_stats). The statistics pass reads flat arenas, so lists that are not arena views are
-    packed first (a copy of every operand, as populations above 64 workers already cost), and a
-    guarded step takes at most 64 workers.
+    (state.last_stats). Lists that are not arena views are measured and stepped where they lie
+    (`ops.delta_stats_list`, then `ops.outer_step_list` or, clipped, `ops.outer_step_list_scaled`):
+    nothing of the population's size is allocated, and per_tensor comes with it, the segments being
+    the tensors. A refusal leaves every base tensor and the momentum untouched. A guarded step takes
+    at most 64 workers.
     """
     state = state or OuterState()
     base_params = list(base_params)
@@ -269,7 +312,7 @@ def outer_step(base_params, worker_params, state: OuterState | None = None, lr: 
         flats = [flat_view(w) for w in worker_params]
         if guard is not None and len(worker_params) > L_MAX:
             raise EdtError(f"a guarded step takes at most {L_MAX} workers")
-        if guard is None and (theta is None or any(f is None for f in flats)):
+        if theta is None or any(f is None for f in flats):
             bf16_master = base_params and base_params[0].dtype == torch.bfloat16
             if (cpu_tails is None or bf16_master) and len(worker_params) <= L_MAX and base_params \
                     and all(p.is_cuda for p in base_params):
@@ -277,7 +320,7 @@ def outer_step(base_params, worker_params, state: OuterState | None = None, lr: 
                     raise EdtError("all trained models must share one dtype")
                 tails = _tail_bits(cpu_tails, [p.numel() for p in base_params], base_params[0].device, state,
                                    per_tensor=True)
-                _step_list(base_params, worker_params, state, lr, momentum, nesterov, tails=tails)
+                _step_list(base_params, worker_params, state, lr, momentum, nesterov, tails=tails, guard=guard)
                 return state
         copied = theta is None
         if copied:

@@ -1,6 +1,6 @@
 """The outer guard's host side: the policy, the totals, the decision and the report, as
-pure functions of host numbers (numpy, no device work). `diloco._guard_pass` and
-`distributed.ShardedOuterSync._guarded` launch the statistics kernels and bring their rows to the
+pure functions of host numbers (numpy, no device work). `diloco._guard_pass` (arenas),
+`diloco._guard_pass_list` (separate tensors) and `distributed.ShardedOuterSync._guarded` launch the statistics kernels and bring their rows to the
 host; what they conclude from them is here, once. Totals are float64 sums in one fixed order
 (`sequential_total`), so every rank reaches the same decision."""
 from __future__ import annotations

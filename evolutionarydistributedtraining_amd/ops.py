@@ -107,6 +107,44 @@ def delta_stats(theta: torch.Tensor, workers: list[torch.Tensor], plan: "SlerpPl
     return out[:plan.nchunks * W].view(plan.nchunks, W)
 
 
+def delta_stats_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]], plan: "SlerpPlan") -> torch.Tensor:
+    """`delta_stats` over T separate tensors per model, read where they lie (edt_delta_stats_list,
+    nothing packed): float64 [plan.nchunks, 3 K + 2] on the device, the statistics of the step
+    `outer_step_list(thetas, workers, ...)` would take. plan: `make_slerp_plan(offsets, device,
+    relative=True)` over the tensors' sizes — segment t is tensor t, chunk starts are relative to it.
+    Tensor t's rows equal, bit for bit, `delta_stats` of that tensor alone as a one-segment arena
+    (the lane mapping follows the element's index inside its tensor); against the packed arena the
+    per-chunk bits agree only when every size is a multiple of 8, the totals up to fp64 summation
+    order otherwise. An empty tensor has no chunks. The result is a view of the pooled workspace
+    (`_scratch`): read it before the next call on this stream overwrites it."""
+    lib = L.lib()
+    T, K = len(thetas), len(workers)
+    if K == 0:
+        raise L.EdtError("no workers")
+    if K > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"the statistics pass takes at most {L.EDT_MAX_WORKERS} workers")
+    flat_w, numels, gdt, wdt = _check_list_operands(thetas, workers, None)
+    if not plan.relative or plan.nseg != T or plan.seg_numel.tolist() != numels:
+        raise L.EdtError("the chunk plan must be relative with one segment per tensor, of the tensors' sizes")
+    W = 3 * K + 2
+    if T == 0 or plan.nchunks == 0:
+        return torch.zeros(0, W, dtype=torch.float64, device=thetas[0].device if T else plan.chunks.device)
+    dev = thetas[0].device
+    if plan.chunks.device != dev:
+        raise L.EdtError("the chunk plan lives on another device")
+    out = _scratch(dev, int(lib.edt_delta_stats_doubles(K, plan.nchunks)))
+    nbytes = lib.edt_delta_stats_list_workspace_bytes(T, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    P_ = ctypes.c_void_p
+    th_arr = (P_ * T)(*[t.data_ptr() for t in thetas])
+    w_arr = (P_ * len(flat_w))(*[t.data_ptr() for t in flat_w])
+    numel = (ctypes.c_uint64 * T)(*numels)
+    L.check(lib.edt_delta_stats_list(th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, numel, T,
+                                     L.ptr(plan.chunks), plan.nchunks, L.ptr(out), L.ptr(ws), nbytes,
+                                     L.stream_ptr(dev)), "edt_delta_stats_list")
+    return out[:plan.nchunks * W].view(plan.nchunks, W)
+
+
 def outer_step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]],
                     momenta: list[torch.Tensor] | None, has_momentum: bool, lr: float,
                     momentum_coef: float, nesterov: bool, tails=None) -> None:
@@ -115,22 +153,29 @@ def outer_step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]
     momenta[t] (theta's dtype, required when momentum_coef != 0), all updated in place.
     tails: (bits, byte offsets) from torchcompat.torch_cpu_tail_bits_per_tensor — the reference
     host's bf16 scalar tails per tensor (edt_outer_step_list_tail; bf16 master only)."""
-    lib = L.lib()
-    T, K = len(thetas), len(workers)
-    if K == 0:
-        raise L.EdtError("no workers")
-    if K > L.EDT_MAX_WORKERS:
-        raise L.EdtError(f"tensor-list step takes at most {L.EDT_MAX_WORKERS} workers")
+    _outer_step_list(thetas, workers, momenta, has_momentum, lr, momentum_coef, nesterov, tails)
+
+
+def outer_step_list_scaled(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]],
+                           momenta: list[torch.Tensor] | None, has_momentum: bool, lr: float,
+                           momentum_coef: float, nesterov: bool, grad_scale: float, tails=None) -> None:
+    """`outer_step_list` with a clipped pseudo-gradient (edt_outer_step_list_scaled): grad =
+    round((-acc) * grad_scale), `outer_step_scaled`'s rule per tensor. grad_scale: finite, in [0, 1];
+    1.0 gives outer_step_list's bits."""
+    _outer_step_list(thetas, workers, momenta, has_momentum, lr, momentum_coef, nesterov, tails, float(grad_scale))
+
+
+def _check_list_operands(thetas, workers, momenta) -> tuple:
+    """The operand checks of the tensor-list entries: (flat worker list, sizes, theta's dtype, the
+    workers' dtype). One comprehension per property over all T x (K + 2) tensors (the drop-in path
+    sees model.parameters() lists: hundreds of tensors per model, so per-tensor Python matters)."""
+    T = len(thetas)
     if any(len(w) != T for w in workers):
         raise L.EdtError("every worker needs one tensor per parameter")
-    if momentum_coef != 0 and momenta is None:
-        raise L.EdtError("momentum tensors are required when momentum != 0")
     if momenta is not None and len(momenta) != T:
         raise L.EdtError("one momentum tensor per parameter")
     if T == 0:
-        return
-    # one comprehension per property over all T x (K + 2) tensors (the drop-in path sees
-    # model.parameters() lists: hundreds of tensors per model, so per-tensor Python matters)
+        return [], [], None, None
     flat_w = [t for w in workers for t in w]
     every = thetas + flat_w + (list(momenta) if momenta is not None else [])
     if not all([t.is_cuda for t in every]):
@@ -152,6 +197,23 @@ def outer_step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]
     if momenta is not None:
         if [t.numel() for t in momenta] != numels or {t.dtype for t in momenta} != {gdt}:
             raise L.EdtError("momentum tensors must match the parameters' sizes and dtype")
+    return flat_w, numels, gdt, wdt
+
+
+# One body for the three list entries: plain, with tail masks, scaled (grad_scale given; its tail
+# arguments are nullable).
+def _outer_step_list(thetas, workers, momenta, has_momentum, lr, momentum_coef, nesterov, tails, *grad_scale) -> None:
+    lib = L.lib()
+    T, K = len(thetas), len(workers)
+    if K == 0:
+        raise L.EdtError("no workers")
+    if K > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"tensor-list step takes at most {L.EDT_MAX_WORKERS} workers")
+    if momentum_coef != 0 and momenta is None:
+        raise L.EdtError("momentum tensors are required when momentum != 0")
+    flat_w, numels, gdt, wdt = _check_list_operands(thetas, workers, momenta)
+    if T == 0:
+        return
     numel = (ctypes.c_uint64 * T)(*numels)
     nbytes = lib.edt_outer_list_workspace_bytes(T, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=thetas[0].device)
@@ -159,23 +221,26 @@ def outer_step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]
     th_arr = (P_ * T)(*[t.data_ptr() for t in thetas])
     w_arr = (P_ * len(flat_w))(*[t.data_ptr() for t in flat_w])
     m_arr = (P_ * T)(*[t.data_ptr() for t in momenta]) if momenta is not None else None
-    if tails is None:
-        L.check(lib.edt_outer_step_list(th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, m_arr,
-                                        int(has_momentum), numel, T, float(lr), float(momentum_coef), int(nesterov),
-                                        L.ptr(ws), nbytes, L.stream_ptr(thetas[0].device)), "edt_outer_step_list")
-        return
-    bits, offs = tails
-    if gdt != torch.bfloat16:
-        raise L.EdtError("scalar-tail bits apply to a bf16 master only")
-    if len(offs) != T or not bits.is_cuda or bits.dtype != torch.uint8 or bits.device != thetas[0].device:
-        raise L.EdtError("tails: a uint8 device mask and one byte offset per tensor")
-    if any(o + (n + 7) // 8 > bits.numel() for o, n in zip(offs, numels)):
-        raise L.EdtError("tails: the mask does not cover every tensor")
-    toff = (ctypes.c_uint64 * T)(*[int(o) for o in offs])
-    L.check(lib.edt_outer_step_list_tail(th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, m_arr,
-                                         int(has_momentum), numel, T, float(lr), float(momentum_coef), int(nesterov),
-                                         L.ptr(bits), toff, L.ptr(ws), nbytes, L.stream_ptr(thetas[0].device)),
-            "edt_outer_step_list_tail")
+    head = (th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, m_arr, int(has_momentum), numel, T, float(lr),
+            float(momentum_coef), int(nesterov))
+    tail = (L.ptr(ws), nbytes, L.stream_ptr(thetas[0].device))
+    bits, toff = None, None
+    if tails is not None:
+        bits, offs = tails
+        if gdt != torch.bfloat16:
+            raise L.EdtError("scalar-tail bits apply to a bf16 master only")
+        if len(offs) != T or not bits.is_cuda or bits.dtype != torch.uint8 or bits.device != thetas[0].device:
+            raise L.EdtError("tails: a uint8 device mask and one byte offset per tensor")
+        if any(o + (n + 7) // 8 > bits.numel() for o, n in zip(offs, numels)):
+            raise L.EdtError("tails: the mask does not cover every tensor")
+        toff = (ctypes.c_uint64 * T)(*[int(o) for o in offs])
+    if grad_scale:
+        L.check(lib.edt_outer_step_list_scaled(*head, L.ptr(bits), toff, *grad_scale, *tail),
+                "edt_outer_step_list_scaled")
+    elif tails is None:
+        L.check(lib.edt_outer_step_list(*head, *tail), "edt_outer_step_list")
+    else:
+        L.check(lib.edt_outer_step_list_tail(*head, L.ptr(bits), toff, *tail), "edt_outer_step_list_tail")
 
 
 def delta_partial(theta: torch.Tensor, workers: list[torch.Tensor], k_total: int,

@@ -160,6 +160,47 @@ int edt_outer_step_list_tail(void* const* theta_t, int gdt, const void* const* t
                              double lr, double momentum, int nesterov, const uint8_t* tail_bits,
                              const uint64_t* tail_byte_offset, void* workspace, uint64_t workspace_bytes,
                              void* stream);
+/* edt_outer_step_list_tail with a clipped pseudo-gradient (edt_outer_step_scaled's rule on
+ * separate tensors): grad = round_g((-acc) * grad_scale), one fp32 multiply rounded to theta's
+ * dtype, then the unchanged SGD update. grad_scale must be finite and in [0, 1] (EDT_ERR_ARG
+ * otherwise, nothing written); 1.0f gives edt_outer_step_list(_tail)'s bits. tail_bits and
+ * tail_byte_offset may be NULL (no tail emulation); given, gdt must be EDT_BF16. The workspace is
+ * edt_outer_step_list's (edt_outer_list_workspace_bytes). */
+int edt_outer_step_list_scaled(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
+                               void* const* momentum_t, int has_momentum, const uint64_t* numel, int T,
+                               double lr, double momentum, int nesterov, const uint8_t* tail_bits,
+                               const uint64_t* tail_byte_offset, float grad_scale, void* workspace,
+                               uint64_t workspace_bytes, void* stream);
+
+/* Tensor-list form of edt_delta_stats: the statistics of the step edt_outer_step_list would take
+ * on T separate tensors, read where they lie (nothing is packed, nothing is written but `out` and
+ * `workspace`).
+ *   theta_t[T], theta_k[K * T], numel[T]   host arrays as edt_outer_step_list's (worker-major;
+ *                               numel[t] == 0 allowed: such a tensor has no chunks and its
+ *                               pointers are not read)
+ *   chunk_desc (device)         nchunks chunks {start, length, segment}: segment s is tensor s,
+ *                               start is RELATIVE to the tensor (edt_slerp_make_chunks over the
+ *                               tensors' prefix sums, each start minus its tensor's offset), a
+ *                               chunk never crosses a tensor, start + length <= numel[segment]
+ *   out (device, 8-byte aligned, edt_delta_stats_doubles(K, nchunks) doubles): the chunk rows
+ *                               [nchunks][3 K + 2] in edt_delta_stats' layout, then row scratch
+ *   workspace (device, 8-byte aligned, >= edt_delta_stats_list_workspace_bytes(T, K)): receives
+ *                               the pointer table by a stream-ordered copy, so it must not be
+ *                               reused before the launch has run
+ * Numerics: the rows of tensor t's chunks equal, bit for bit, the rows edt_delta_stats gives for
+ * that tensor alone as an arena of one segment [0, numel[t]): the same d_k, m, masking and counts,
+ * and the canonical chunk-sum order with the tile and lane mapping taken from the element's index
+ * INSIDE ITS TENSOR (a tensor's aligned body starts at its element 0: no head, a tail of < 8
+ * elements). Against edt_delta_stats over the tensors packed into one arena the per-chunk bits
+ * agree only when every numel[t] is a multiple of 8 (else the arena's chunk starts are off 8 and
+ * its lanes hold other elements); the totals then differ by fp64 summation order alone.
+ * A tensor whose K + 1 pointers are all 16-byte aligned takes vector loads, any other scalar loads
+ * in the same lane mapping: the bits do not depend on alignment. S_km is formed for K <= 8.
+ * 1 <= K <= EDT_MAX_WORKERS, T >= 0 (T == 0 or nchunks == 0: nothing to do). */
+uint64_t edt_delta_stats_list_workspace_bytes(int T, int K);
+int edt_delta_stats_list(const void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
+                         const uint64_t* numel, int T, const uint64_t* chunk_desc, int64_t nchunks, double* out,
+                         void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* Partial delta sum for the sharded multi-GPU step (EDT_LM/diloco.py:243-246 restricted to the
  * workers resident on this rank): acc_f32[i] (+)= sum_{k<K_local} round_g((theta_k - theta_g)/K_total).
