@@ -71,6 +71,14 @@ SIGNATURES = [
                                     ctypes.c_uint32, _U64, _P]),
     ("edt_sgd_delta_sum_q_sr", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _I, _U64, _U64,
                                     ctypes.c_uint32, _U64, _P]),
+    ("edt_partial_sum_stats_q", _I, [ctypes.POINTER(_P), _I, _I, _I, _U64, _P, ctypes.c_int64, _P, _P]),
+    ("edt_sgd_apply_sum_q_scaled", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, ctypes.c_float,
+                                        _P]),
+    ("edt_sgd_delta_sum_q_scaled", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _P, _I,
+                                        ctypes.c_float, _P]),
+    ("edt_sgd_delta_sum_q_sr_scaled", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _P, _I, _U64, _D, _D, _I, _P, _I, _U64,
+                                           _U64, ctypes.c_uint32, _U64, ctypes.c_float, _P]),
+    ("edt_delta_partial_q_to", _I, [_P, _I, ctypes.POINTER(_P), _I, _I, _I, _U64, _U64, _I, _P, _P, _P, _P]),
     ("edt_pair_merge", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_to", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_pair_merge_population", _I, [ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P),

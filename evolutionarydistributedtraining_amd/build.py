@@ -22,7 +22,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("edt_outer.hip", "edt_merge.hip", "ed
                                            "edt_quant.hip", "edt_stats.hip")]
 HEADER = os.path.join(ROOT, "include", "edt_sync.h")
 DEPS = SOURCES + [HEADER, os.path.join(CSRC, "edt_common.h"), os.path.join(CSRC, "edt_step.h"),
-                  os.path.join(CSRC, "edt_chunksum.h")]
+                  os.path.join(CSRC, "edt_chunksum.h"), os.path.join(CSRC, "edt_mx.h")]
 OUT = os.path.join(PKG_DIR, "libedt_sync.so")
 
 ARCH = "gfx950"

@@ -41,6 +41,7 @@
 // covers 512 elements = 16 blocks, and sizes are multiples of 512 so every wave is whole. Payload
 // leaves as one 8-byte (MXFP8) or 4-byte (MXFP4) store per lane, contiguous across the wave; the
 // 16 scale bytes of a wave are gathered across lanes into four dwords stored by lanes 0/16/32/48.
+#include "edt_mx.h"
 #include "edt_step.h"
 
 namespace {
@@ -51,7 +52,7 @@ struct QWorkers {
 
 struct QPartialArgs {
     const void* theta;
-    float* residual;         // error feedback (EF): read, added, rewritten
+    float* residual;         // error feedback (EF): read, added, rewritten (the _to kernel: read only)
     uint8_t* packed;         // [region][payload | scales]
     uint64_t n;
     uint64_t tiles_per_region;   // region_elems / 512
@@ -64,18 +65,11 @@ struct QPartialArgs {
     __device__ __forceinline__ const void* wp(int k) const { return w.p[k]; }
 };
 
-// element formats: mantissa bits, smallest normal exponent, exponent bias, largest magnitude, emax
-template <int FMT> struct QFmt;
-template <> struct QFmt<EDT_MXFP8> {
-    static constexpr int MB = 3, EMIN = -6, BIAS = 7, EMAX = 8, BITS = 8;
-    static constexpr float MAXV = 448.f;
+// edt_delta_partial_q_to's block: the new residual goes to a second buffer. It trails, so the
+// in-place kernels keep their argument block.
+struct QPartialArgsTo : QPartialArgs {
+    float* residual_out;
 };
-template <> struct QFmt<EDT_MXFP4> {
-    static constexpr int MB = 1, EMIN = 0, BIAS = 1, EMAX = 2, BITS = 4;
-    static constexpr float MAXV = 6.f;
-};
-
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }   // -126 <= e <= 127
 
 // stochastic rounding: the Philox key (the seed) and what of the counter is the same for a whole call
 struct QSr {
@@ -120,15 +114,6 @@ __device__ __forceinline__ uint32_t q_code(float r) {
     using F = QFmt<FMT>;
     if (r < pow2f(F::EMIN)) return (uint32_t)(r * pow2f(F::MB - F::EMIN));       // zero and subnormals
     return (__float_as_uint(r) >> (23 - F::MB)) - ((uint32_t)(127 - F::BIAS) << F::MB);
-}
-
-// magnitude code -> value
-template <int FMT>
-__device__ __forceinline__ float q_decode(uint32_t c) {
-    using F = QFmt<FMT>;
-    if (FMT == EDT_MXFP8 && c == 0x7fu) return __builtin_nanf("");                  // OCP E4M3's NaN
-    if (c < (1u << F::MB)) return (float)c * pow2f(F::EMIN - F::MB);
-    return __uint_as_float((c + ((uint32_t)(127 - F::BIAS) << F::MB)) << (23 - F::MB));
 }
 
 // The quantize-and-store tail shared by phase 1 and phase 2': the 8 values v at element `off` of the
@@ -234,8 +219,10 @@ __device__ __forceinline__ RegionOf region_of(uint64_t i, uint64_t tiles_per_reg
 
 // Phase 1 for the 8 elements at i (a multiple of 8; the wave's 64 lanes cover 512 consecutive ones):
 // edt_delta_partial's partial (add_delta per worker, the rounded quotients summed in fp32), quantized.
+// res_out: where the new residual goes (EF): a.residual itself, or the _to kernel's second buffer.
 template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF, int RND = EDT_ROUND_NEAREST>
-__device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t i, const QSr& sr = QSr{}) {
+__device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, float* res_out, uint64_t i,
+                                                const QSr& sr = QSr{}) {
     constexpr int N = kVec;
     float g[N], acc[N];
     ld<GDT, N, (EDT_NT_RMW != 0)>(a.theta, i, g);
@@ -257,61 +244,46 @@ __device__ __forceinline__ void partial_q_elems(const QPartialArgs& a, uint64_t 
         for (int j = 0; j < N; ++j) acc[j] = acc[j] + r[j];          // p' = p + r
     }
     const RegionOf r = region_of(i, a.tiles_per_region);
-    quant_store<FMT, EF, RND>(acc, a.residual, i, a.packed + r.reg * a.region_bytes, r.off, a.payload_bytes, sr);
+    quant_store<FMT, EF, RND>(acc, res_out, i, a.packed + r.reg * a.region_bytes, r.off, a.payload_bytes, sr);
 }
 
 template <int GDT, int WDT, int KC, int DIV, int FMT, bool EF>
 __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_kernel(QPartialArgs a) {
-    for_whole_waves(a.n, [&](uint64_t i) { partial_q_elems<GDT, WDT, KC, DIV, FMT, EF>(a, i); });
+    for_whole_waves(a.n, [&](uint64_t i) { partial_q_elems<GDT, WDT, KC, DIV, FMT, EF>(a, a.residual, i); });
+}
+
+// the transactional phase 1 (edt_delta_partial_q_to): the same body with error feedback, the
+// residual read from a.residual and the new one written to a.residual_out (another buffer)
+template <int GDT, int WDT, int KC, int DIV, int FMT>
+__global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_to_kernel(QPartialArgsTo a) {
+    for_whole_waves(a.n, [&](uint64_t i) { partial_q_elems<GDT, WDT, KC, DIV, FMT, true>(a, a.residual_out, i); });
 }
 
 // phase 1 with stochastic rounding: the same partial, no residual, the draw of each lane's group
 template <int GDT, int WDT, int KC, int DIV, int FMT>
 __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void delta_partial_q_sr_kernel(QPartialArgs a, QSr sr) {
     for_whole_waves(a.n, [&](uint64_t i) {
-        partial_q_elems<GDT, WDT, KC, DIV, FMT, false, EDT_ROUND_STOCHASTIC>(a, i, sr);
+        partial_q_elems<GDT, WDT, KC, DIV, FMT, false, EDT_ROUND_STOCHASTIC>(a, nullptr, i, sr);
     });
 }
 
 // ---------------------------------------------------------------------------------------
 // phase 2
 
-struct QRegions {
-    const uint8_t* p[EDT_MAX_WORKERS];
-};
+// QRegions and ld_q, a region's decoder: edt_mx.h (shared with the statistics pass)
 
-template <int FMT>
-__device__ __forceinline__ void ld_q(const uint8_t* region, uint64_t n, uint64_t i, float (&x)[kVec]) {
-    using F = QFmt<FMT>;
-    uint32_t code[kVec];
-    if constexpr (FMT == EDT_MXFP8) {
-        const u32x2 v = *reinterpret_cast<const u32x2*>(region + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { code[j] = (v.x >> (8 * j)) & 0xffu; code[4 + j] = (v.y >> (8 * j)) & 0xffu; }
-    } else {
-        const uint32_t v = *reinterpret_cast<const uint32_t*>(region + (i >> 1));
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) code[j] = (v >> (4 * j)) & 0xfu;
-    }
-    const uint32_t sb = region[n * F::BITS / 8 + (i >> 5)];
-    const int e = (int)sb - 127;                         // elem * 2^e as two exact factors
-    const float f0 = pow2f(e < -64 ? -64 : e), f1 = pow2f(e < -64 ? e + 64 : 0);
-#pragma unroll
-    for (int j = 0; j < kVec; ++j) {
-        const uint32_t sign = (code[j] >> (F::BITS - 1)) << 31;
-        const float mag = q_decode<FMT>(code[j] & ((1u << (F::BITS - 1)) - 1u)) * f0 * f1;
-        x[j] = sb == 255u ? __builtin_nanf("") : __uint_as_float(__float_as_uint(mag) | sign);
-    }
-}
-
-// edt_sgd_apply_sum's step (sgd_from_sum) with every rank's partial dequantized from its region
-template <int GDT, int FMT>
+// edt_sgd_apply_sum's step (sgd_from_sum) with every rank's partial dequantized from its region.
+// SC (the *_scaled entries, here and in phase 2'): grad = round_g((-sum) * grad_scale); the clip
+// coefficient is a trailing argument only the SC instantiations have (`scale` is one float with SC,
+// nothing without), so the unscaled kernels keep their argument block, as edt_outer.hip's do.
+template <int GDT, int FMT, bool SC = false, class... S>
 __global__ __launch_bounds__(kBlock) void sgd_apply_sum_q_kernel(void* theta, QRegions P, int np, void* mom,
-                                                                 uint64_t n, SgdScalars s) {
+                                                                 uint64_t n, SgdScalars s, S... scale) {
+    static_assert(sizeof...(S) == (SC ? 1 : 0), "one grad_scale with SC, none without");
     for_whole_waves(n, [&](uint64_t i) {
         float g0[kVec], g[kVec];
-        sgd_from_sum<GDT, kVec>(theta, mom, i, s, np, [&](int r, float (&x)[kVec]) { ld_q<FMT>(P.p[r], n, i, x); },
-                                g0, g);
+        sgd_from_sum<GDT, kVec, SC>(theta, mom, i, s, np, [&](int r, float (&x)[kVec]) { ld_q<FMT>(P.p[r], n, i, x); },
+                                    g0, g, scale...);
         st<GDT, kVec>(theta, i, g);
     });
 }
@@ -319,14 +291,15 @@ __global__ __launch_bounds__(kBlock) void sgd_apply_sum_q_kernel(void* theta, QR
 // phase 2': sgd_apply_sum_q_kernel's step on the owned shard, but theta stays as it is: the update
 // u = theta' - theta (+ the owner's residual with EF) leaves as one region of FOUT blocks, rounded
 // to nearest (with or without EF) or stochastically (RND, no residual)
-template <int GDT, int FIN, int FOUT, bool EF, int RND>
+template <int GDT, int FIN, int FOUT, bool EF, int RND, bool SC = false, class... S>
 __device__ __forceinline__ void delta_sum_q_body(const void* theta, const QRegions& P, int np, void* mom, uint64_t n,
                                                  const SgdScalars& s, float* residual, uint8_t* packed_out,
-                                                 const QSr& sr) {
+                                                 const QSr& sr, S... scale) {
     const uint64_t payload = n / 8 * QFmt<FOUT>::BITS;
     for_whole_waves(n, [&](uint64_t i) {
         float g0[kVec], g[kVec], u[kVec];
-        sgd_from_sum<GDT, kVec>(theta, mom, i, s, np, [&](int r, float (&x)[kVec]) { ld_q<FIN>(P.p[r], n, i, x); }, g0, g);
+        sgd_from_sum<GDT, kVec, SC>(theta, mom, i, s, np, [&](int r, float (&x)[kVec]) { ld_q<FIN>(P.p[r], n, i, x); },
+                                    g0, g, scale...);
 #pragma unroll
         for (int j = 0; j < kVec; ++j) u[j] = g[j] - g0[j];               // u = theta' - theta
         if constexpr (EF) {
@@ -339,18 +312,22 @@ __device__ __forceinline__ void delta_sum_q_body(const void* theta, const QRegio
     });
 }
 
-template <int GDT, int FIN, int FOUT, bool EF>
+template <int GDT, int FIN, int FOUT, bool EF, bool SC = false, class... S>
 __global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_kernel(const void* theta, QRegions P, int np, void* mom,
                                                                  uint64_t n, SgdScalars s, float* residual,
-                                                                 uint8_t* packed_out) {
-    delta_sum_q_body<GDT, FIN, FOUT, EF, EDT_ROUND_NEAREST>(theta, P, np, mom, n, s, residual, packed_out, QSr{});
+                                                                 uint8_t* packed_out, S... scale) {
+    static_assert(sizeof...(S) == (SC ? 1 : 0), "one grad_scale with SC, none without");
+    delta_sum_q_body<GDT, FIN, FOUT, EF, EDT_ROUND_NEAREST, SC>(theta, P, np, mom, n, s, residual, packed_out, QSr{},
+                                                                scale...);
 }
 
-template <int GDT, int FIN, int FOUT>
+template <int GDT, int FIN, int FOUT, bool SC = false, class... S>
 __global__ __launch_bounds__(kBlock) void sgd_delta_sum_q_sr_kernel(const void* theta, QRegions P, int np, void* mom,
                                                                     uint64_t n, SgdScalars s, uint8_t* packed_out,
-                                                                    QSr sr) {
-    delta_sum_q_body<GDT, FIN, FOUT, false, EDT_ROUND_STOCHASTIC>(theta, P, np, mom, n, s, nullptr, packed_out, sr);
+                                                                    QSr sr, S... scale) {
+    static_assert(sizeof...(S) == (SC ? 1 : 0), "one grad_scale with SC, none without");
+    delta_sum_q_body<GDT, FIN, FOUT, false, EDT_ROUND_STOCHASTIC, SC>(theta, P, np, mom, n, s, nullptr, packed_out, sr,
+                                                                      scale...);
 }
 
 // phase 3: theta <- round_g(theta + D(q)) over a bucket of n / region_elems regions back to back.
@@ -381,13 +358,22 @@ __global__ __launch_bounds__(kBlock) void apply_delta_q_kernel(void* theta, cons
 
 inline int fmt_bits(int fmt) { return fmt == EDT_MXFP8 ? 8 : fmt == EDT_MXFP4 ? 4 : 0; }
 
-int launch_partial_q(int gdt, int wdt, int fmt, const QPartialArgs& a, const QSr* sr, bool div_exact, hipStream_t s) {
+// residual_out: the _to kernel (error feedback into a second buffer); null: in place
+int launch_partial_q(int gdt, int wdt, int fmt, const QPartialArgs& a, const QSr* sr, bool div_exact, hipStream_t s,
+                     float* residual_out = nullptr) {
     const unsigned g = grid_for(a.n, true);
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_fmt(fmt, [&](auto F) {
             return with_kc_div<KC_QUANT>(a.K, div_exact, [&](auto KC, auto DIV) {
                 constexpr int GDT = decltype(G)::value, WDT = decltype(W)::value, FMT = decltype(F)::value;
                 constexpr int KCV = decltype(KC)::value, DIVV = decltype(DIV)::value;
+                if (residual_out) {
+                    QPartialArgsTo to;
+                    static_cast<QPartialArgs&>(to) = a;
+                    to.residual_out = residual_out;
+                    delta_partial_q_to_kernel<GDT, WDT, KCV, DIVV, FMT><<<g, kBlock, 0, s>>>(to);
+                    return check_launch("delta_partial_q_to_kernel");
+                }
                 if (sr) {
                     delta_partial_q_sr_kernel<GDT, WDT, KCV, DIVV, FMT><<<g, kBlock, 0, s>>>(a, *sr);
                     return check_launch("delta_partial_q_sr_kernel");
@@ -401,20 +387,30 @@ int launch_partial_q(int gdt, int wdt, int fmt, const QPartialArgs& a, const QSr
     });
 }
 
+// scale: the scaled entries' clip coefficient (the SC instantiations); null: the plain kernels
 int launch_delta_sum_q(int gdt, int fmt_in, int fmt_out, const void* theta, const QRegions& P, int np, void* mom,
-                       uint64_t n, const SgdScalars& sc, float* residual, uint8_t* out, const QSr* sr, hipStream_t s) {
+                       uint64_t n, const SgdScalars& sc, float* residual, uint8_t* out, const QSr* sr,
+                       const float* scale, hipStream_t s) {
     const unsigned g = grid_for(n, true);
     return with_dtype(gdt, [&](auto G) {
         return with_fmt(fmt_in, [&](auto FI) {
             return with_fmt(fmt_out, [&](auto FO) {
                 constexpr int GDT = decltype(G)::value, FIN = decltype(FI)::value, FOUT = decltype(FO)::value;
                 if (sr) {
-                    sgd_delta_sum_q_sr_kernel<GDT, FIN, FOUT><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, *sr);
+                    if (scale)
+                        sgd_delta_sum_q_sr_kernel<GDT, FIN, FOUT, true>
+                            <<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, *sr, *scale);
+                    else
+                        sgd_delta_sum_q_sr_kernel<GDT, FIN, FOUT><<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, out, *sr);
                     return check_launch("sgd_delta_sum_q_sr_kernel");
                 }
                 return with_bool(residual != nullptr, [&](auto EF) {
-                    sgd_delta_sum_q_kernel<GDT, FIN, FOUT, decltype(EF)::value>
-                        <<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out);
+                    if (scale)
+                        sgd_delta_sum_q_kernel<GDT, FIN, FOUT, decltype(EF)::value, true>
+                            <<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out, *scale);
+                    else
+                        sgd_delta_sum_q_kernel<GDT, FIN, FOUT, decltype(EF)::value>
+                            <<<g, kBlock, 0, s>>>(theta, P, np, mom, n, sc, residual, out);
                     return check_launch("sgd_delta_sum_q_kernel");
                 });
             });
@@ -471,10 +467,11 @@ uint64_t edt_q_region_bytes(uint64_t region_elems, int fmt) {
     return region_elems / 8 * bits + region_elems / 32;
 }
 
-// edt_delta_partial_q (sr null) and edt_delta_partial_q_sr: one validation, one argument block
+// edt_delta_partial_q (sr null), edt_delta_partial_q_sr and edt_delta_partial_q_to (residual_out:
+// another buffer than residual): one validation, one argument block
 static int delta_partial_q_impl(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
                                 int K_total, uint64_t n, uint64_t region_elems, int fmt, float* residual, void* packed,
-                                const QSr* sr, uint64_t elem_base, void* stream) {
+                                const QSr* sr, uint64_t elem_base, void* stream, float* residual_out = nullptr) {
     g_err[0] = 0;
     if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
     if (int rc = check_fmt(fmt)) return rc;
@@ -489,7 +486,7 @@ static int delta_partial_q_impl(const void* theta_g, int gdt, const void* const*
     if (!packed) return fail(EDT_ERR_ARG, "packed is null");
     QPartialArgs a;
     memset(&a, 0, sizeof(a));
-    bool al = aligned16(theta_g) && aligned16(packed) && aligned16(residual);
+    bool al = aligned16(theta_g) && aligned16(packed) && aligned16(residual) && aligned16(residual_out);
     if (int rc = fill_table(a.w.p, theta_k, K_local, "theta_k", al)) return rc;
     if (!al) return fail(EDT_ERR_ARG, "the quantized partial needs 16-byte aligned operands");
     a.theta = theta_g;
@@ -502,7 +499,7 @@ static int delta_partial_q_impl(const void* theta_g, int gdt, const void* const*
     a.K = K_local;
     a.kdiv = (float)K_total;
     a.kinv = 1.0f / (float)K_total;
-    return launch_partial_q(gdt, wdt, fmt, a, sr, !is_pow2(K_total), (hipStream_t)stream);
+    return launch_partial_q(gdt, wdt, fmt, a, sr, !is_pow2(K_total), (hipStream_t)stream, residual_out);
 }
 
 int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
@@ -510,6 +507,22 @@ int edt_delta_partial_q(const void* theta_g, int gdt, const void* const* theta_k
                         void* stream) {
     return delta_partial_q_impl(theta_g, gdt, theta_k, wdt, K_local, K_total, n, region_elems, fmt, residual, packed,
                                 nullptr, 0, stream);
+}
+
+int edt_delta_partial_q_to(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                           int K_total, uint64_t n, uint64_t region_elems, int fmt, const float* residual_in,
+                           float* residual_out, void* packed, void* stream) {
+    g_err[0] = 0;
+    if (n != 0 && (!residual_in || !residual_out))
+        return fail(EDT_ERR_ARG, "residual_in / residual_out is null (without error feedback: edt_delta_partial_q)");
+    float* in = const_cast<float*>(residual_in);       // the _to kernel only reads it
+    if (residual_in == residual_out)                    // in place: edt_delta_partial_q itself
+        return delta_partial_q_impl(theta_g, gdt, theta_k, wdt, K_local, K_total, n, region_elems, fmt, in, packed,
+                                    nullptr, 0, stream);
+    if (bytes_overlap(residual_in, n * sizeof(float), residual_out, n * sizeof(float)))
+        return fail(EDT_ERR_ARG, "residual_out overlaps residual_in (the same buffer, or clear of it)");
+    return delta_partial_q_impl(theta_g, gdt, theta_k, wdt, K_local, K_total, n, region_elems, fmt, in, packed,
+                                nullptr, 0, stream, residual_out);
 }
 
 int edt_delta_partial_q_sr(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
@@ -520,11 +533,16 @@ int edt_delta_partial_q_sr(const void* theta_g, int gdt, const void* const* thet
                                 &sr, elem_base, stream);
 }
 
-int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
-                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
+// edt_sgd_apply_sum_q (scale null) and edt_sgd_apply_sum_q_scaled (the clip coefficient is checked
+// first, so a refused call writes nothing)
+static int sgd_apply_sum_q_impl(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
+                                int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                                const float* scale, void* stream) {
     g_err[0] = 0;
     if (int rc = check_master_dtype(gdt)) return rc;
     if (int rc = check_fmt(fmt)) return rc;
+    if (scale)
+        if (int rc = check_grad_scale(*scale)) return rc;
     if (int rc = check_partial_count(nacc)) return rc;
     if (int rc = check_one_region(n)) return rc;
     if (n == 0) return EDT_OK;
@@ -540,20 +558,39 @@ int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int 
     hipStream_t st = (hipStream_t)stream;
     return with_dtype(gdt, [&](auto G) {
         return with_fmt(fmt, [&](auto F) {
-            sgd_apply_sum_q_kernel<decltype(G)::value, decltype(F)::value>
-                <<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
+            if (scale)
+                sgd_apply_sum_q_kernel<decltype(G)::value, decltype(F)::value, true>
+                    <<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s, *scale);
+            else
+                sgd_apply_sum_q_kernel<decltype(G)::value, decltype(F)::value>
+                    <<<g, kBlock, 0, st>>>(theta_g, P, nacc, momentum, n, s);
             return check_launch("sgd_apply_sum_q_kernel");
         });
     });
 }
 
-// edt_sgd_delta_sum_q (sr null) and edt_sgd_delta_sum_q_sr
+int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
+                        int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream) {
+    return sgd_apply_sum_q_impl(theta_g, gdt, regions, nacc, fmt, momentum, has_momentum, n, lr, momentum_coef, nesterov,
+                                nullptr, stream);
+}
+
+int edt_sgd_apply_sum_q_scaled(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
+                               int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                               float grad_scale, void* stream) {
+    return sgd_apply_sum_q_impl(theta_g, gdt, regions, nacc, fmt, momentum, has_momentum, n, lr, momentum_coef, nesterov,
+                                &grad_scale, stream);
+}
+
+// edt_sgd_delta_sum_q (sr null) and edt_sgd_delta_sum_q_sr; scale: their scaled forms' coefficient
 static int sgd_delta_sum_q_impl(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
                                 void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
                                 int nesterov, float* residual, void* packed_out, int fmt_out, const QSr* sr,
-                                uint64_t elem_base, void* stream) {
+                                uint64_t elem_base, void* stream, const float* scale = nullptr) {
     g_err[0] = 0;
     if (int rc = check_master_dtype(gdt)) return rc;
+    if (scale)
+        if (int rc = check_grad_scale(*scale)) return rc;
     if (int rc = check_fmt(fmt_in)) return rc;
     if (int rc = check_fmt(fmt_out)) return rc;
     if (int rc = check_partial_count(nacc)) return rc;
@@ -570,7 +607,7 @@ static int sgd_delta_sum_q_impl(const void* theta_g, int gdt, const void* const*
     if (int rc = fill_table(P.p, regions, nacc, "regions", al)) return rc;
     if (!al) return fail(EDT_ERR_ARG, "the quantized update needs 16-byte aligned operands");
     return launch_delta_sum_q(gdt, fmt_in, fmt_out, theta_g, P, nacc, momentum, n, s, residual,
-                              static_cast<uint8_t*>(packed_out), sr, (hipStream_t)stream);
+                              static_cast<uint8_t*>(packed_out), sr, scale, (hipStream_t)stream);
 }
 
 int edt_sgd_delta_sum_q(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in, void* momentum,
@@ -587,6 +624,23 @@ int edt_sgd_delta_sum_q_sr(const void* theta_g, int gdt, const void* const* regi
     const QSr sr = make_sr(seed, step, stream_id, elem_base);
     return sgd_delta_sum_q_impl(theta_g, gdt, regions, nacc, fmt_in, momentum, has_momentum, n, lr, momentum_coef,
                                 nesterov, nullptr, packed_out, fmt_out, &sr, elem_base, stream);
+}
+
+int edt_sgd_delta_sum_q_scaled(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
+                               void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
+                               int nesterov, float* residual, void* packed_out, int fmt_out, float grad_scale,
+                               void* stream) {
+    return sgd_delta_sum_q_impl(theta_g, gdt, regions, nacc, fmt_in, momentum, has_momentum, n, lr, momentum_coef,
+                                nesterov, residual, packed_out, fmt_out, nullptr, 0, stream, &grad_scale);
+}
+
+int edt_sgd_delta_sum_q_sr_scaled(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
+                                  void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
+                                  int nesterov, void* packed_out, int fmt_out, uint64_t seed, uint64_t step,
+                                  uint32_t stream_id, uint64_t elem_base, float grad_scale, void* stream) {
+    const QSr sr = make_sr(seed, step, stream_id, elem_base);
+    return sgd_delta_sum_q_impl(theta_g, gdt, regions, nacc, fmt_in, momentum, has_momentum, n, lr, momentum_coef,
+                                nesterov, nullptr, packed_out, fmt_out, &sr, elem_base, stream, &grad_scale);
 }
 
 // edt_apply_delta_q (nbcast = 0: bcast and wdt unused) and edt_apply_delta_q_bcast: one validation

@@ -7,6 +7,7 @@
 // The per-element arithmetic is edt_step.h's (delta_of, mean_add: add_delta's two halves), the
 // sums' order edt_chunksum.h's (the canonical chunk-sum order).
 #include "edt_chunksum.h"
+#include "edt_mx.h"
 #include "edt_step.h"
 
 namespace {
@@ -357,6 +358,72 @@ int launch_partial_stats(PartialStatsArgs a, hipStream_t s) {
     return EDT_OK;
 }
 
+// ---- the same figures of the quantized schedule (reduce_q): the partials are packed regions ------
+// edt_partial_sum_stats_q: m = round_g(rank_sum of D(q_r)), ld_q per rank (edt_mx.h) where
+// partial_sum_stats_kernel loads fp32 — exactly the value edt_sgd_apply_sum_q / edt_sgd_delta_sum_q
+// negate into the gradient, quantization error and residuals included. Read only. The same unit,
+// tile, lane and tree mapping; a lane's 8 elements are the quantized kernels' (four lanes share a
+// scale byte). n % 512 == 0 and the chunk bounds are multiples of 8, so a chunk is its aligned
+// body: no head, no tail, no scalar path. A scale-255 block is 32 NaN elements: left out, counted.
+struct PartialStatsQArgs {
+    const uint64_t* chunks;
+    double* rows;
+    uint64_t units;
+    uint64_t u0;
+    uint64_t n;          // elements of one region
+    int np;
+    QRegions P;
+};
+
+template <int GDT, int FMT, int NPC>
+__global__ __launch_bounds__(kBlock) void partial_sum_stats_q_kernel(PartialStatsQArgs a) {
+    __shared__ double part[kWavesPerBlock][kPartialStatsWidth];
+    const uint64_t u = a.u0 + blockIdx.x;
+    if (u >= a.units) return;                         // the whole workgroup
+    const int np = NPC > 0 ? NPC : a.np;
+    const int wave = threadIdx.x >> 6;
+    const uint64_t c = u / kStatsUpc;
+    const int tile = (int)(u % kStatsUpc) * kWavesPerBlock + wave;
+    const uint64_t start = a.chunks[3 * c], len = a.chunks[3 * c + 1];
+    const uint64_t A = (start + kVec - 1) / kVec * kVec, B = (start + len) / kVec * kVec;
+    const uint64_t i = A + (uint64_t)tile * kTileElems + (uint64_t)(threadIdx.x & 63) * kVec;
+    // inside the chunk, and never past the region whatever the table says
+    const bool has_vec = i < B && i + kVec <= a.n;
+
+    // a lane without a vector sums zeros: m = +0, finite, adds nothing
+    float m[kVec];
+    rank_sum(np, m, [&](int r, float (&x)[kVec]) {
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) x[j] = 0.f;
+        if (has_vec) ld_q<FMT>(a.P.p[r], a.n, i, x);
+    });
+    rnd<GDT>(m);
+    double smm = 0.0, cm = 0.0;
+    mask_count(m, cm);
+    dot_chain(m, m, smm);
+    const double v[2] = {smm, cm};
+    double r[Red<2>::N2];
+    tile_reduce<2>(v, r);
+    red_store<2>(r, [&](int idx, double x) { part[wave][idx] = x; });
+    __syncthreads();
+    double* out = a.rows + unit_slot(u, a.units) * (uint64_t)kPartialStatsWidth;
+    if (threadIdx.x < kPartialStatsWidth) {
+        const int q = threadIdx.x;
+        out[q] = (part[0][q] + part[1][q]) + (part[2][q] + part[3][q]);
+    }
+}
+
+template <int GDT, int FMT, int NPC>
+int launch_partial_stats_q(PartialStatsQArgs a, hipStream_t s) {
+    const uint64_t units = a.units;
+    for (uint64_t u0 = 0; u0 < units; u0 += kUnitGridCap) {
+        a.u0 = u0;
+        partial_sum_stats_q_kernel<GDT, FMT, NPC><<<unit_grid(units - u0), kBlock, 0, s>>>(a);
+        if (int rc = check_launch("partial_sum_stats_q_kernel")) return rc;
+    }
+    return EDT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -397,6 +464,49 @@ int edt_partial_sum_stats(const float* const* acc_f32, int nacc, int gdt, uint64
                 case 4: return launch_partial_stats<GD, 4, VEC>(a, s);
                 case 8: return launch_partial_stats<GD, 8, VEC>(a, s);
                 default: return launch_partial_stats<GD, 0, VEC>(a, s);
+            }
+        });
+    });
+    if (rc) return rc;
+    return launch_tree_reduce(a.rows, kPartialStatsWidth, kStatsUpc, kStatsUpc, 1, nchunks, out, s);
+}
+
+// rows and workspace: edt_partial_sum_stats_doubles(nchunks), the same two columns and row levels
+int edt_partial_sum_stats_q(const void* const* regions, int nacc, int fmt, int gdt, uint64_t n,
+                            const uint64_t* chunk_desc, int64_t nchunks, double* out, void* stream) {
+    g_err[0] = 0;
+    int rc = check_master_dtype(gdt);
+    if (!rc && fmt != EDT_MXFP8 && fmt != EDT_MXFP4)
+        rc = fail(EDT_ERR_ARG, "unknown wire format %d (EDT_MXFP8 or EDT_MXFP4)", fmt);
+    if (!rc) rc = check_partial_count(nacc);
+    if (rc) return rc;
+    if (n % 512) return fail(EDT_ERR_ARG, "n = %llu is not a multiple of 512 (one region)", (unsigned long long)n);
+    if (nchunks < 0) return fail(EDT_ERR_ARG, "negative chunk count");
+    if (!regions) return fail(EDT_ERR_ARG, "regions is null");
+    if (n == 0 || nchunks == 0) return EDT_OK;
+    if (!chunk_desc || !out) return fail(EDT_ERR_ARG, "null chunk table or output");
+    if (reinterpret_cast<uintptr_t>(out) & 7u) return fail(EDT_ERR_ARG, "out must be 8-byte aligned");
+    PartialStatsQArgs a;
+    memset(&a, 0, sizeof(a));
+    bool al = true;
+    if ((rc = fill_table(a.P.p, regions, nacc, "regions", al))) return rc;
+    if (!al) return fail(EDT_ERR_ARG, "the packed regions must be 16-byte aligned");
+    a.chunks = chunk_desc;
+    a.rows = out + (uint64_t)nchunks * kPartialStatsWidth;
+    a.units = (uint64_t)nchunks * kStatsUpc;
+    a.n = n;
+    a.np = nacc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = with_dtype(gdt, [&](auto G) {
+        constexpr int GD = decltype(G)::value;
+        return with_fmt(fmt, [&](auto F) {
+            constexpr int FM = decltype(F)::value;
+            switch (nacc) {
+                case 1: return launch_partial_stats_q<GD, FM, 1>(a, s);
+                case 2: return launch_partial_stats_q<GD, FM, 2>(a, s);
+                case 4: return launch_partial_stats_q<GD, FM, 4>(a, s);
+                case 8: return launch_partial_stats_q<GD, FM, 8>(a, s);
+                default: return launch_partial_stats_q<GD, FM, 0>(a, s);
             }
         });
     });

@@ -66,7 +66,7 @@ on the comm stream overlaps the HBM-bound kernels on the compute stream:
                          With broadcast="workers" the step already does it and the flag changes
                          nothing. NaN elements (a scale-255 block) are NaN in theta and in every
                          worker; their payload bits are not specified.
-  guard=OuterGuard       (reduce, reduce_ordered, exact; opt-in) measures, screens and clips the step
+  guard=OuterGuard       (every schedule; opt-in) measures, screens and clips the step
                          across the ranks before theta is touched: every rank forms the
                          same float64 totals in one fixed order (its buckets and chunks in order, then
                          the ranks in rank order after an all_gather_object) and takes the same
@@ -76,6 +76,15 @@ on the comm stream overlaps the HBM-bound kernels on the compute stream:
                          edt_sgd_apply(_sum)_scaled; exact runs edt_delta_stats on the received slices
                          and clips with edt_outer_step_scaled. A refusal leaves theta, the momentum and
                          the worker arenas as they were on every rank, with every collective waited for.
+                         reduce_q screens the same way before phase 1; a rank left without a worker
+                         launches no phase 1, sends zero bytes (every block +0) and keeps its residual;
+                         the mean is measured as it will be applied — the dequantized rank-ordered sum,
+                         quantization error and residuals included (edt_partial_sum_stats_q) — and
+                         clipped by edt_sgd_apply_sum_q_scaled / edt_sgd_delta_sum_q(_sr)_scaled. With
+                         error feedback phase 1 writes the new residual into a second buffer
+                         (edt_delta_partial_q_to; + 4 B per element of memory per rank, no extra
+                         traffic) and the two are swapped only once the step is decided, so a refusal
+                         also leaves `residual`, `residual_g` and `q_step` as they were.
   mode="auto" / broadcast="auto" (defaults) pick the combination with the fewest wire bytes,
   ties to exact, then reduce_ordered: at K = 8 bf16 workers, fp32 theta: N = 2 reduce_ordered/theta
   (8 B/elem), N = 4 and 8 exact/workers (6 and 4 B/elem); all fp32: N = 2 and 4 reduce_ordered,
@@ -117,6 +126,11 @@ class _Verdict(NamedTuple):
 
 
 _NO_GUARD = _Verdict(None, None, None, 1.0)      # every worker, unclipped: what an unguarded step passes
+
+
+class GuardKernelsMissing(EdtError, ValueError):
+    """guard= with mode='reduce_q' on kernels that lack what that schedule's guard needs. Also a
+    ValueError: before those kernels existed the constructor refused the combination with one."""
 
 
 def _scaled(name: str) -> str:
@@ -203,6 +217,7 @@ class ShardedOuterSync:
         self.guard = guard
         self.last_stats = None         # the last guarded step's report, identical on every rank
         self._guard_plans = {}
+        self.gather_format = gather_format
         if guard is not None:
             self._check_guard()
         n = layout.total
@@ -246,7 +261,11 @@ class ShardedOuterSync:
             self.q_send = torch.zeros(self._q_bytes(self.n_pad), dtype=torch.uint8, device=device)
             self.q_recv = torch.zeros(self._q_bytes(self.n_pad), dtype=torch.uint8, device=device)
             self.residual = torch.zeros(self.n_pad, dtype=torch.float32, device=device) if error_feedback else None
-            self.gather_format = gather_format
+            # a guarded step with error feedback writes the new residual here and swaps the two
+            # once the step is decided (`_commit_residual`): a refusal leaves `residual` as it was
+            self._residual_next = (torch.zeros(self.n_pad, dtype=torch.float32, device=device)
+                                   if error_feedback and guard is not None else None)
+            self._residual_pending = False
             if gather_format is not None:
                 # the owners' updates of a bucket, [src rank][payload | scales], from byte
                 # _q_bytes(b, gather_format); this rank writes its own slot, the all-gather the rest
@@ -284,28 +303,28 @@ class ShardedOuterSync:
         """The constructor's refusals of guard=: each says what is missing."""
         if not isinstance(self.guard, OuterGuard):
             raise TypeError("guard must be an OuterGuard")
-        if self.mode == "reduce_q":
-            raise ValueError("guard= does not take mode='reduce_q': a dropped worker or a refused step would have "
-                             "to take back what phase 1 already folded into the error-feedback residuals (and the "
-                             "stochastic q_step), which that schedule does not define yet (DESIGN §9)")
         if self.guard.per_tensor:
             raise ValueError("guard.per_tensor is not available on the sharded step: shards cut tensors, so no "
                              "rank holds a tensor's rows")
         if self.k_total > 64:
             raise EdtError(f"a guarded step takes at most 64 workers in all, not {self.k_total}")
         k = self.kernels
-        need = ["make_slerp_plan", "delta_stats"] + ([] if self.mode == "exact" else ["partial_sum_stats"])
+        measure = {"exact": [], "reduce_q": ["partial_sum_stats_q"]}.get(self.mode, ["partial_sum_stats"])
+        need = ["make_slerp_plan", "delta_stats"] + measure
         need.append(_scaled(self._step_name()))
         missing = [m for m in need if not hasattr(k, m)]
         if missing:
-            raise EdtError(f"guard= with mode={self.mode!r} needs kernels that provide {need}; "
-                           f"{type(k).__name__ if not hasattr(k, '__name__') else k.__name__} lacks {missing}")
+            err = GuardKernelsMissing if self.mode == "reduce_q" else EdtError
+            raise err(f"guard= with mode={self.mode!r} needs kernels that provide {need}; "
+                      f"{type(k).__name__ if not hasattr(k, '__name__') else k.__name__} lacks {missing}")
 
     def _step_name(self) -> str:
         """The entry that steps an owned shard in this schedule, before `_entry` picks its plain or
         scaled form. Without sgd_apply_sum (stand-in kernels) reduce_ordered sums in torch."""
         if self.mode == "exact":
             return "outer_step"
+        if self.mode == "reduce_q":           # phase 2, or phase 2' of the quantized gather
+            return "sgd_apply_sum_q" if self.gather_format is None else "sgd_delta_sum_q"
         if self.mode == "reduce_ordered" and hasattr(self.kernels, "sgd_apply_sum"):
             return "sgd_apply_sum"
         return "sgd_apply"
@@ -314,8 +333,9 @@ class ShardedOuterSync:
         """Algorithmic HBM bytes the guard adds to one step on this rank (no drop; kernel_bytes()
         keeps its meaning). Reduce schedules: edt_delta_stats over the local arenas (theta and the
         K_local workers, whole arena) and edt_partial_sum_stats over the owned shards' partials (N
-        of them, reduce: the one reduced shard); exact: edt_delta_stats over the owned shards with
-        all K received slices. 0 without a guard."""
+        of them, reduce: the one reduced shard; reduce_q: edt_partial_sum_stats_q over the N packed
+        regions, q bytes per element each); exact: edt_delta_stats over the owned shards with all K
+        received slices. The shadow residual of reduce_q adds memory, no traffic. 0 without a guard."""
         if self.guard is None:
             return 0
         wb = self.worker_bufs[0].element_size()
@@ -323,6 +343,8 @@ class ShardedOuterSync:
         shard = self.n_pad // self.world
         if self.mode == "exact":
             return shard * (self.k_total * wb + gb)
+        if self.mode == "reduce_q":
+            return self.n_pad * (self.k_local * wb + gb) + self.world * self._q_bytes(shard)
         nacc = self.world if self.mode == "reduce_ordered" else 1
         return self.n_pad * (self.k_local * wb + gb) + shard * 4 * nacc
 
@@ -492,16 +514,28 @@ class ShardedOuterSync:
         if clip is None:                        # cannot happen: every survivor was finite
             raise EdtError("the survivors' statistics flagged a worker")
         rep["clip_coef"] = clip
+        self._commit_residual()                 # the step is decided: nothing below refuses
         v = self._verdict(survivors, clip)
         return [consume(*owned, v) for owned in self._owned()]
+
+    def _commit_residual(self):
+        """reduce_q with error feedback: a guarded phase 1 wrote the new residual into the second
+        buffer; the step has been decided, so the two swap. Per rank: a rank that launched no
+        phase 1 (no surviving worker) keeps its residual."""
+        if self.mode == "reduce_q" and self._residual_pending:
+            self.residual, self._residual_next = self._residual_next, self.residual
+            self._residual_pending = False
 
     def _guard_reduce(self, produce):
         """Reduce schedules. Before any exchange, edt_delta_stats over the local workers and the
         whole arena gives every worker's S_kk and non-finite count (its local-mean columns are
         ignored: the mean is not known where the deltas are); gathered, global worker index
         rank * K_local + j; the policy screens the workers with nothing in flight. Then phase 1 over
-        the survivors and every exchange, and the mean's statistics from what the owners hold."""
+        the survivors and every exchange, and the mean's statistics from what the owners hold
+        (reduce_q: of the dequantized regions, the value phase 2 applies)."""
         kl, K = self.k_local, self.k_total
+        if self.mode == "reduce_q":
+            self._residual_pending = False      # a refused step's second buffer is simply overwritten
         rows = torch.as_tensor(self._launch(self.kernels.delta_stats, self.theta_buf, list(self.worker_bufs),
                                             self._stats_plan(self.n_pad)))
         t = sequential_total(rows.cpu().numpy(), 3 * kl + 2)                     # host sync 1 of 2
@@ -516,10 +550,15 @@ class ShardedOuterSync:
         self._exchange(produce, self._verdict(survivors, 1.0))
         rows = []
         for b, e, s0, s1, _, _ in self._owned():
-            parts = ([self._acc_out(b, e)] if self.mode == "reduce"
-                     else list(self.acc_recv[b:e].view(self.world, s1 - s0)))
-            rows.append(torch.as_tensor(self._launch(self.kernels.partial_sum_stats, parts, self.theta_buf.dtype,
-                                                     self._stats_plan(s1 - s0))).clone())
+            if self.mode == "reduce_q":
+                got = self._launch(self.kernels.partial_sum_stats_q, self._q_regions(b, e), self.wire_format,
+                                   self.theta_buf.dtype, self._stats_plan(s1 - s0))
+            else:
+                parts = ([self._acc_out(b, e)] if self.mode == "reduce"
+                         else list(self.acc_recv[b:e].view(self.world, s1 - s0)))
+                got = self._launch(self.kernels.partial_sum_stats, parts, self.theta_buf.dtype,
+                                   self._stats_plan(s1 - s0))
+            rows.append(torch.as_tensor(got).clone())
         t = self._rank_totals(rows, 2)                                           # host sync 2 of 2
         totals["S_mm"], totals["nonfinite_mean"] = float(t[0]), int(t[1])
         self.last_stats.update(report(totals))
@@ -601,19 +640,42 @@ class ShardedOuterSync:
     # reduce_q: reduce_ordered with quantized partials: phase 1 writes bucket [b, e) as `world`
     # packed regions [dest rank][payload | scales] (the fp32 partial stays in registers), the
     # all-to-all moves the bytes; phase 2 dequantizes the owned shard's N regions
+    # A guarded step (`v` from the screening): phase 1 over this rank's survivors, divided by the
+    # number of survivors in all; a rank with none launches nothing, sends the wire format's zero
+    # (scale byte 0, codes 0: D = +0 everywhere) and keeps its residual; with error feedback the new
+    # residual goes to the second buffer until `_commit_residual`
     def _produce_reduce_q(self, b, e, v):
         qb, qe = self._q_bytes(b), self._q_bytes(e)
-        self._launch(self.kernels.delta_partial_q, self.theta_buf[b:e], [w[b:e] for w in self.worker_bufs],
-                     self.k_total, self.q_send[qb:qe], (e - b) // self.world, self.wire_format,
-                     None if self.residual is None else self.residual[b:e], **self._sr(0, b))
+        workers, k_total = self.worker_bufs, self.k_total
+        if v.local is not None:
+            workers, k_total = [self.worker_bufs[j] for j in v.local], v.divisor
+        if not workers:
+            self.q_send[qb:qe].zero_()
+        else:
+            kw = self._sr(0, b)
+            if self.guard is not None and self.residual is not None:
+                if self._residual_next is None:
+                    raise EdtError("guard= on reduce_q with error feedback must be given to the constructor "
+                                   "(it allocates the second residual buffer)")
+                kw["residual_out"] = self._residual_next[b:e]
+                self._residual_pending = True
+            self._launch(self.kernels.delta_partial_q, self.theta_buf[b:e], [w[b:e] for w in workers],
+                         k_total, self.q_send[qb:qe], (e - b) // self.world, self.wire_format,
+                         None if self.residual is None else self.residual[b:e], **kw)
         return [self.comm.all_to_all(self.q_recv[qb:qe], self.q_send[qb:qe], async_op=True)]
+
+    def _q_regions(self, b, e):
+        """The owned shard's `world` received regions of bucket [b, e), in rank order."""
+        per = (e - b) // self.world
+        return list(self.q_recv[self._q_bytes(b):self._q_bytes(e)].view(self.world, self._q_bytes(per)))
 
     def _consume_reduce_q(self, b, e, s0, s1, mom, sl, v):
         k, per = self.kernels, s1 - s0
-        regions = list(self.q_recv[self._q_bytes(b):self._q_bytes(e)].view(self.world, self._q_bytes(per)))
+        regions = self._q_regions(b, e)
+        name, scale = _entry(self._step_name(), v.clip)
         if self.gather_format is None:
-            self._launch(k.sgd_apply_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
-                         self.has_momentum, self.lr, self.momentum, self.nesterov)
+            self._launch(getattr(k, name), self.theta_buf[s0:s1], regions, self.wire_format, mom,
+                         self.has_momentum, self.lr, self.momentum, self.nesterov, *scale)
             return self._gather(b, e, s0, s1)
         # phase 2': the quantized update of the owned shard into this rank's slot of u_recv (theta
         # untouched), then the all-gather of the packed bytes
@@ -621,8 +683,9 @@ class ShardedOuterSync:
         ub, ur = self._q_bytes(b, gf), self._q_bytes(per, gf)
         slot = self.u_recv[ub + self.rank * ur:ub + (self.rank + 1) * ur]
         res_g = None if self.residual_g is None else self.residual_g[sl]
-        self._launch(k.sgd_delta_sum_q, self.theta_buf[s0:s1], regions, self.wire_format, mom,
-                     self.has_momentum, self.lr, self.momentum, self.nesterov, slot, gf, res_g, **self._sr(1, s0))
+        self._launch(getattr(k, name), self.theta_buf[s0:s1], regions, self.wire_format, mom,
+                     self.has_momentum, self.lr, self.momentum, self.nesterov, slot, gf, *scale, res_g,
+                     **self._sr(1, s0))
         src = slot if self.inplace else slot.clone()
         return self.comm.all_gather(self.u_recv[ub:self._q_bytes(e, gf)], src, async_op=True)
 

@@ -431,28 +431,39 @@ def _stochastic(rounding, residual, seed, step, stream_id, elem_base) -> bool:
 
 def delta_partial_q(theta: torch.Tensor, workers: list[torch.Tensor], k_total: int, packed: torch.Tensor,
                     region_elems: int, fmt, residual: torch.Tensor | None = None, rounding: str = "nearest",
-                    seed: int = 0, step: int = 0, stream_id: int = 0, elem_base: int = 0) -> None:
+                    seed: int = 0, step: int = 0, stream_id: int = 0, elem_base: int = 0,
+                    residual_out: torch.Tensor | None = None) -> None:
     """delta_partial's fp32 partial, block-quantized (fmt: 'mxfp8' | 'mxfp4', include/edt_sync.h)
     into `packed` (uint8) as theta.numel() / region_elems regions back to back; the fp32 partial
     never reaches HBM. residual (fp32, theta's size): error feedback, added before and rewritten
     after the quantization (edt_delta_partial_q). rounding='stochastic' (edt_delta_partial_q_sr, no
     residual): element i draws the Philox bits of (seed, step, stream_id, global element
-    elem_base + i); elem_base is a multiple of 8."""
+    elem_base + i); elem_base is a multiple of 8.
+    residual_out (with residual; fp32, theta's size): the new residual goes there and `residual` is
+    only read (edt_delta_partial_q_to: a step that may still be refused commits by swapping the
+    two); the same tensor as `residual` is the in-place form."""
     lib = L.lib()
     sr = _stochastic(rounding, residual, seed, step, stream_id, elem_base)
     if not workers:
         raise L.EdtError("no workers")
-    L.require_device(theta, packed, residual, *workers)
+    L.require_device(theta, packed, residual, residual_out, *workers)
     n = theta.numel()
     _check_workers(theta, workers)
     code = _qfmt(fmt)
     _check_packed(packed, n, region_elems, fmt)
     _check_residual(residual, n)
+    _check_residual(residual_out, n)
+    if residual_out is not None and residual is None:
+        raise L.EdtError("residual_out needs residual (error feedback): there is no residual to write without it")
     head = (L.ptr(theta), L.dtype_code(theta), L.ptr_array(workers), L.dtype_code(workers[0]), len(workers),
             int(k_total), n, int(region_elems), code)
     if sr:
         L.check(lib.edt_delta_partial_q_sr(*head, L.ptr(packed), int(seed), int(step), int(stream_id), int(elem_base),
                                            L.stream_ptr(theta.device)), "edt_delta_partial_q_sr")
+        return
+    if residual_out is not None:
+        L.check(lib.edt_delta_partial_q_to(*head, L.ptr(residual), L.ptr(residual_out), L.ptr(packed),
+                                           L.stream_ptr(theta.device)), "edt_delta_partial_q_to")
         return
     L.check(lib.edt_delta_partial_q(*head, L.ptr(residual), L.ptr(packed), L.stream_ptr(theta.device)),
             "edt_delta_partial_q")
@@ -463,15 +474,59 @@ def sgd_apply_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt, momen
     """sgd_apply_sum on quantized partials: each of `regions` (uint8, q_region_bytes(theta.numel()))
     is dequantized, they are summed in list order in fp32, then the SGD step on theta
     (edt_sgd_apply_sum_q: the reduce_q schedule's per-shard step)."""
+    _sgd_apply_sum_q("edt_sgd_apply_sum_q", theta, regions, fmt, momentum, has_momentum, lr, momentum_coef, nesterov)
+
+
+def sgd_apply_sum_q_scaled(theta: torch.Tensor, regions: list[torch.Tensor], fmt, momentum: torch.Tensor | None,
+                           has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool,
+                           grad_scale: float) -> None:
+    """`sgd_apply_sum_q` with a clipped pseudo-gradient (edt_sgd_apply_sum_q_scaled; sgd_apply_scaled's
+    rule on the dequantized rank-ordered sum). grad_scale: finite, in [0, 1]; 1.0 gives
+    sgd_apply_sum_q's bits."""
+    _sgd_apply_sum_q("edt_sgd_apply_sum_q_scaled", theta, regions, fmt, momentum, has_momentum, lr, momentum_coef,
+                     nesterov, float(grad_scale))
+
+
+def _sgd_apply_sum_q(entry: str, theta, regions, fmt, momentum, has_momentum, lr, momentum_coef, nesterov,
+                     *grad_scale) -> None:
     lib = L.lib()
     L.require_device(theta, momentum, *regions)
     n = theta.numel()
     code = _qfmt(fmt)
     _check_regions(regions, n, fmt)
     _check_momentum(momentum, theta)
-    L.check(lib.edt_sgd_apply_sum_q(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code,
-                                    L.ptr(momentum), int(has_momentum), n, float(lr), float(momentum_coef),
-                                    int(nesterov), L.stream_ptr(theta.device)), "edt_sgd_apply_sum_q")
+    L.check(getattr(lib, entry)(L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code,
+                                L.ptr(momentum), int(has_momentum), n, float(lr), float(momentum_coef),
+                                int(nesterov), *grad_scale, L.stream_ptr(theta.device)), entry)
+
+
+def partial_sum_stats_q(regions: list[torch.Tensor], fmt, gdt_like, plan: "SlerpPlan") -> torch.Tensor:
+    """`partial_sum_stats` of the mean `sgd_apply_sum_q(theta, regions, fmt, ...)` (or
+    `sgd_delta_sum_q`) would apply, read only (edt_partial_sum_stats_q): float64 [plan.nchunks, 2] on
+    the device, S_mm | nonfinite_mean, of m = round(((D(q_0) + D(q_1)) + ...)) in the dtype of
+    `gdt_like` — quantization error and residuals included; a scale-255 block counts 32. regions:
+    uint8 buffers of q_region_bytes(n, fmt) each, n = plan.seg_offsets[-1] elements (a multiple of
+    512). plan: `make_slerp_plan([0, n], device)`; its chunk bounds must be multiples of 8. The
+    result is a view of the pooled workspace (`_scratch`): read it before the next call on this
+    stream overwrites it."""
+    lib = L.lib()
+    if not regions:
+        raise L.EdtError("no regions")
+    L.require_device(*regions)
+    if len(regions) > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"the statistics pass takes at most {L.EDT_MAX_WORKERS} regions")
+    code = _qfmt(fmt)
+    n = int(plan.seg_offsets[-1])
+    _check_regions(regions, n, fmt)
+    dev = regions[0].device
+    _check_stats_plan(plan, n, dev, "a region's")
+    if plan.chunk_elems % 8 or any(o % 8 for o in plan.seg_offsets):
+        raise L.EdtError("the chunk plan of packed regions must cut at multiples of 8 elements")
+    out = _scratch(dev, int(lib.edt_partial_sum_stats_doubles(plan.nchunks)))
+    L.check(lib.edt_partial_sum_stats_q(L.ptr_array(regions), len(regions), code, L.dtype_code(gdt_like), n,
+                                        L.ptr(plan.chunks), plan.nchunks, L.ptr(out), L.stream_ptr(dev)),
+            "edt_partial_sum_stats_q")
+    return out[:plan.nchunks * 2].view(plan.nchunks, 2)
 
 
 def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, momentum: torch.Tensor | None,
@@ -485,6 +540,27 @@ def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, mo
     (edt_sgd_delta_sum_q: the quantized gather's phase 2'). rounding='stochastic'
     (edt_sgd_delta_sum_q_sr, no residual): delta_partial_q's keywords, elem_base being the shard's
     start in the arena."""
+    _sgd_delta_sum_q(("edt_sgd_delta_sum_q", "edt_sgd_delta_sum_q_sr"), theta, regions, fmt_in, momentum, has_momentum, lr, momentum_coef,
+                     nesterov, packed_out, fmt_out, residual, rounding, seed, step, stream_id, elem_base)
+
+
+def sgd_delta_sum_q_scaled(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, momentum: torch.Tensor | None,
+                           has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool,
+                           packed_out: torch.Tensor, fmt_out, grad_scale: float,
+                           residual: torch.Tensor | None = None, rounding: str = "nearest", seed: int = 0,
+                           step: int = 0, stream_id: int = 0, elem_base: int = 0) -> None:
+    """`sgd_delta_sum_q` with a clipped pseudo-gradient (edt_sgd_delta_sum_q_scaled, or
+    edt_sgd_delta_sum_q_sr_scaled with rounding='stochastic'): the step is sgd_apply_sum_q_scaled's,
+    and its update theta' - theta is quantized as before. grad_scale: finite, in [0, 1]; 1.0 gives
+    sgd_delta_sum_q's bits."""
+    _sgd_delta_sum_q(("edt_sgd_delta_sum_q_scaled", "edt_sgd_delta_sum_q_sr_scaled"), theta, regions, fmt_in, momentum, has_momentum, lr, momentum_coef,
+                     nesterov, packed_out, fmt_out, residual, rounding, seed, step, stream_id, elem_base,
+                     float(grad_scale))
+
+
+# entries: the wrapper's nearest-rounding entry and its stochastic partner
+def _sgd_delta_sum_q(entries: tuple, theta, regions, fmt_in, momentum, has_momentum, lr, momentum_coef, nesterov,
+                     packed_out, fmt_out, residual, rounding, seed, step, stream_id, elem_base, *grad_scale) -> None:
     lib = L.lib()
     sr = _stochastic(rounding, residual, seed, step, stream_id, elem_base)
     L.require_device(theta, momentum, packed_out, residual, *regions)
@@ -497,12 +573,13 @@ def sgd_delta_sum_q(theta: torch.Tensor, regions: list[torch.Tensor], fmt_in, mo
     _check_residual(residual, n)
     head = (L.ptr(theta), L.dtype_code(theta), L.ptr_array(regions), len(regions), code_in, L.ptr(momentum),
             int(has_momentum), n, float(lr), float(momentum_coef), int(nesterov))
+    entry = entries[int(sr)]
     if sr:
-        L.check(lib.edt_sgd_delta_sum_q_sr(*head, L.ptr(packed_out), code_out, int(seed), int(step), int(stream_id),
-                                           int(elem_base), L.stream_ptr(theta.device)), "edt_sgd_delta_sum_q_sr")
+        L.check(getattr(lib, entry)(*head, L.ptr(packed_out), code_out, int(seed), int(step), int(stream_id),
+                                    int(elem_base), *grad_scale, L.stream_ptr(theta.device)), entry)
         return
-    L.check(lib.edt_sgd_delta_sum_q(*head, L.ptr(residual), L.ptr(packed_out), code_out, L.stream_ptr(theta.device)),
-            "edt_sgd_delta_sum_q")
+    L.check(getattr(lib, entry)(*head, L.ptr(residual), L.ptr(packed_out), code_out, *grad_scale,
+                                L.stream_ptr(theta.device)), entry)
 
 
 def _check_bcast(theta: torch.Tensor, outs) -> None:

@@ -346,6 +346,51 @@ int edt_sgd_delta_sum_q_sr(const void* theta_g, int gdt, const void* const* regi
                            void* packed_out, int fmt_out, uint64_t seed, uint64_t step, uint32_t stream_id,
                            uint64_t elem_base, void* stream);
 
+/* ---- the guard on reduce_q: measure, clip, and a phase 1 that can be taken back ----
+ * Statistics of the mean pseudo-gradient edt_sgd_apply_sum_q / edt_sgd_delta_sum_q are about to
+ * apply, read-only: edt_partial_sum_stats with every partial dequantized from its region,
+ *   m = round_g(((D(q_0) + D(q_1)) + ...) + D(q_{nacc-1}))     (fp32 adds in that order)
+ * quantization error and residuals included. regions[0..nacc): device pointers to packed regions
+ * of n elements each in fmt, 16-byte aligned; n % 512 == 0. chunk_desc (device): nchunks chunks over
+ * [0, n) whose starts and lengths are multiples of 8 (edt_slerp_make_chunks over a shard gives
+ * such a table), so there is no scalar path. out (device, 8-byte aligned,
+ * edt_partial_sum_stats_doubles(nchunks) doubles — the same rows and workspace as the fp32 form):
+ * the chunk rows [nchunks][2] = S_mm | nonfinite_mean, then the row scratch. The same canonical
+ * chunk-sum order, so S_mm equals edt_partial_sum_stats on the dequantized fp32 arrays bit for
+ * bit. A scale-255 block is 32 NaN elements: they add nothing to S_mm and are counted.
+ * EDT_ERR_ARG for an unknown fmt or gdt, nacc outside [1, 64], n % 512 != 0, a null or misaligned
+ * pointer. */
+int edt_partial_sum_stats_q(const void* const* regions, int nacc, int fmt, int gdt, uint64_t n,
+                            const uint64_t* chunk_desc, int64_t nchunks, double* out, void* stream);
+
+/* Phase 2 and phase 2' with a clipped pseudo-gradient (edt_sgd_apply_sum_scaled's rule on the
+ * dequantized rank-ordered sum): grad = round_g((-a) * grad_scale), one fp32 multiply rounded to
+ * theta's dtype, then the unchanged SGD update — and, in phase 2', the unchanged quantization of
+ * u = theta' - theta. grad_scale must be finite and in [0, 1] (EDT_ERR_ARG otherwise, nothing
+ * written); 1.0f gives the unscaled entry's bits (theta or the packed update, the momentum, the
+ * residual). Everything else as the unscaled entries. */
+int edt_sgd_apply_sum_q_scaled(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
+                               int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov,
+                               float grad_scale, void* stream);
+int edt_sgd_delta_sum_q_scaled(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
+                               void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
+                               int nesterov, float* residual, void* packed_out, int fmt_out, float grad_scale,
+                               void* stream);
+int edt_sgd_delta_sum_q_sr_scaled(const void* theta_g, int gdt, const void* const* regions, int nacc, int fmt_in,
+                                  void* momentum, int has_momentum, uint64_t n, double lr, double momentum_coef,
+                                  int nesterov, void* packed_out, int fmt_out, uint64_t seed, uint64_t step,
+                                  uint32_t stream_id, uint64_t elem_base, float grad_scale, void* stream);
+
+/* edt_delta_partial_q with error feedback whose new residual goes to a second buffer (the
+ * transactional phase 1: a caller that may refuse the step keeps residual_in and swaps the two
+ * buffers only when it commits): p' = p + residual_in is quantized and residual_out = p' - D(q).
+ * residual_in is only read. Both are n floats, 16-byte aligned and non-null (without error feedback
+ * use edt_delta_partial_q); residual_in == residual_out is edt_delta_partial_q bit for bit, any
+ * other overlap is EDT_ERR_ARG. The packed bytes are edt_delta_partial_q's. */
+int edt_delta_partial_q_to(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,
+                           int K_total, uint64_t n, uint64_t region_elems, int fmt, const float* residual_in,
+                           float* residual_out, void* packed, void* stream);
+
 /* Phase 3 over a bucket of n elements: theta = round_g(f32(theta) + D(q)), one fp32 add then RNE to
  * theta's dtype. `packed` holds n / region_elems regions back to back, each of region_elems
  * elements ([src rank][payload | scales]: the mirror of edt_delta_partial_q's layout). The same call
