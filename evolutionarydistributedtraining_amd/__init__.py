@@ -8,11 +8,13 @@ Replaces the reference's Python/PyTorch-CPU hot path (BarryFutureman/Evolutionar
 with fused HIP kernels for gfx950 behind the C ABI in include/edt_sync.h (libedt_sync.so).
 """
 from ._lib import EdtError, load_library
-from .diloco import DILOCO_DEFAULTS, DILOCO_SIM_DEFAULTS, OuterState, OuterSync, outer_step
+from .diloco import DILOCO_DEFAULTS, DILOCO_SIM_DEFAULTS, OuterState, OuterSync, outer_step, outer_step_fragment
+from .fragments import FragmentPlan
 from .params import ParamArena, ParamLayout, arena_of_module, bind_module_
 
 __all__ = [
     "EdtError", "load_library", "OuterState", "OuterSync", "outer_step", "DILOCO_DEFAULTS",
     "DILOCO_SIM_DEFAULTS", "ParamArena", "ParamLayout", "arena_of_module", "bind_module_",
+    "FragmentPlan", "outer_step_fragment",
 ]
 __version__ = "0.1.0"

@@ -50,6 +50,9 @@ SIGNATURES = [
     ("edt_outer_step_list_scaled", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, _I, ctypes.POINTER(_P), _I,
                                         ctypes.POINTER(_U64), _I, _D, _D, _I, _P, ctypes.POINTER(_U64),
                                         ctypes.c_float, _P, _U64, _P]),
+    ("edt_outer_list_mix_workspace_bytes", _U64, [_I, _I, _I]),
+    ("edt_outer_step_list_mix", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, _I, ctypes.POINTER(_P), _I,
+                                     ctypes.POINTER(_U64), _I, _D, _D, _I, ctypes.POINTER(_P), _I, _D, _P, _U64, _P]),
     ("edt_delta_stats_list_workspace_bytes", _U64, [_I, _I]),
     ("edt_delta_stats_list", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, _I, ctypes.POINTER(_U64), _I, _P,
                                   ctypes.c_int64, _P, _P, _U64, _P]),

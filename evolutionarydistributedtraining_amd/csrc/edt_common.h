@@ -419,6 +419,20 @@ __device__ __forceinline__ void lerp_elems(const void* v0, const void* v1, void*
     st<ODT, N, NTS>(out, i, x);
 }
 
+// lerp_elems' rule on values already in registers (the fused merge of edt_outer_step_list_mix):
+// x = round(round(c0 * x) + y), where y = round(c1 * v1) is formed once by the caller for all of its
+// destinations. lerp_elems keeps its own text (lerp_kernel's code does not move); the two are held
+// together by the test that the fused merge equals ops.lerp bit for bit (tests/test_gpu_fragment.py).
+template <int CDT, int N>
+__device__ __forceinline__ void lerp_held(float (&x)[N], const float (&y)[N], float c0) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = c0 * x[j];
+    rnd<CDT>(x);
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = x[j] + y[j];
+    rnd<CDT>(x);
+}
+
 
 // ---------------------------------------------------------------------------------------
 // host-side dispatch helpers

@@ -3,6 +3,8 @@
 // probe, with their C ABI entries (include/edt_sync.h).
 #include "edt_step.h"
 
+#include <algorithm>
+
 namespace {
 
 // ---------------------------------------------------------------------------------------
@@ -57,6 +59,21 @@ struct TensorArgs {
 struct TensorArgsScaled : TensorArgs {
     float grad_scale;
 };
+// the mixing list step's run (MX): the merge destinations live[j * T + t], j < nmix, in the worker
+// dtype, and lerp's two coefficients beside the same fields
+struct TensorArgsMix : TensorArgs {
+    void* const* live;
+    int nmix;
+    float c0, c1;
+    __device__ __forceinline__ void* lp(int j) const { return live[(uint64_t)j * T + t]; }
+};
+
+// MX: what the step does with theta_new beyond storing it (edt_outer_step_list_mix).
+//   MX_BLEND  every destination is loaded and blended (it may be a worker this thread has read)
+//   MX_HELD   destination j IS worker j and nmix == K (KC > 0): the values the delta loaded are
+//             blended from registers, no second load
+//   MX_COPY   mix == 1: the destination is not read, round_w(theta_new) is stored (BC's stores)
+enum MixKind : int { MX_NONE = 0, MX_BLEND = 1, MX_HELD = 2, MX_COPY = 3 };
 
 // MODE_CHAIN = MODE_FUSED for populations above EDT_MAX_WORKERS: launches of <= 64 workers
 // carry the running sum in theta's dtype (lossless: it is rounded to that dtype after every add).
@@ -65,9 +82,12 @@ enum { MODE_FUSED = 0, MODE_PARTIAL = 1, MODE_CHAIN = 2 };
 // Per-element accumulation acc = sum_k round(round(w_k - g) / K) in the precision of GDT
 // (worker-major order, EDT_LM/diloco.py:243-246). MODE_PARTIAL sums the rounded quotients
 // in fp32 instead (the cross-rank sum is then an fp32 RCCL reduction).
-template <int GDT, int WDT, int KC, int DIV, int MODE, int N, class A, int H2 = 4, bool BC = false, bool SC = false>
+template <int GDT, int WDT, int KC, int DIV, int MODE, int N, class A, int H2 = 4, bool BC = false, bool SC = false,
+          int MX = MX_NONE>
 __device__ __forceinline__ void outer_elems(const A& a, uint64_t i) {
+    static_assert(MX != MX_HELD || KC > 0, "the held form needs a compile-time worker count");
     float g[N], acc[N], b_in[N];
+    [[maybe_unused]] float held[MX == MX_HELD ? KC : 1][N];      // MX_HELD: every worker's values as loaded
     ld<GDT, N, (EDT_NT_RMW != 0), H2>(a.theta, i, g);
     if constexpr (MODE != MODE_PARTIAL) ld_momentum<GDT, N, H2>(a.mom, i, a.sgd, b_in);
     if (MODE == MODE_PARTIAL && a.accumulate) {
@@ -79,8 +99,11 @@ __device__ __forceinline__ void outer_elems(const A& a, uint64_t i) {
         for (int j = 0; j < N; ++j) acc[j] = 0.f;
     }
     const int K = KC > 0 ? KC : a.K;
-    auto body = [&](int k) { add_delta<GDT, WDT, DIV, N, H2, MODE != MODE_PARTIAL>(a, k, g, acc, i); };
-    if constexpr (KC > 0) {
+    [[maybe_unused]] auto body = [&](int k) { add_delta<GDT, WDT, DIV, N, H2, MODE != MODE_PARTIAL>(a, k, g, acc, i); };
+    if constexpr (MX == MX_HELD) {
+#pragma unroll
+        for (int k = 0; k < KC; ++k) add_delta<GDT, WDT, DIV, N, H2, MODE != MODE_PARTIAL>(a, k, g, acc, i, held[k]);
+    } else if constexpr (KC > 0) {
 #pragma unroll
         for (int k = 0; k < KC; ++k) body(k);
     } else {
@@ -108,6 +131,37 @@ __device__ __forceinline__ void outer_elems(const A& a, uint64_t i) {
             // destination may be a worker this thread just read (same elements, same thread).
 #pragma unroll 4
             for (int k = 0; k < a.nbc; ++k) st<WDT, N, (EDT_NT_STORES != 0), H2>(const_cast<void*>(a.bc.p[k]), i, g);
+        }
+        if constexpr (MX != MX_NONE) {
+            // Streaming DiLoCo's merge fused in: every destination, which has usually trained on
+            // since the delta's snapshot was taken, moves towards v = round_w(theta_new) (what BC
+            // stores) by lerp_elems' rule in the worker dtype. A destination may be a worker this
+            // thread has just read (same elements, same thread), as BC's may.
+            rnd<WDT>(g);
+            if constexpr (MX == MX_COPY) {                           // mix == 1: the destination is not read
+#pragma unroll 4
+                for (int j = 0; j < a.nmix; ++j) st<WDT, N, (EDT_NT_STORES != 0), H2>(a.lp(j), i, g);
+            } else {
+                float y[N];                                          // round_w(c1 * v): one for every destination
+#pragma unroll
+                for (int j = 0; j < N; ++j) y[j] = a.c1 * g[j];
+                rnd<WDT>(y);
+                if constexpr (MX == MX_HELD) {
+#pragma unroll
+                    for (int k = 0; k < KC; ++k) {
+                        lerp_held<WDT, N>(held[k], y, a.c0);
+                        st<WDT, N, (EDT_NT_STORES != 0), H2>(a.lp(k), i, held[k]);
+                    }
+                } else {
+#pragma unroll 4
+                    for (int j = 0; j < a.nmix; ++j) {
+                        float x[N];
+                        ld<WDT, N, false, H2>(a.lp(j), i, x);
+                        lerp_held<WDT, N>(x, y, a.c0);
+                        st<WDT, N, (EDT_NT_STORES != 0), H2>(a.lp(j), i, x);
+                    }
+                }
+            }
         }
     }
 }
@@ -170,9 +224,24 @@ struct ListArgs {
 struct ListArgsScaled : ListArgs {
     float grad_scale;
 };
+// edt_outer_step_list_mix's block (MX): the merge's arguments trail, as grad_scale does
+struct ListArgsMix : ListArgs {
+    void* const* live;          // nmix * T, destination-major, worker dtype
+    int nmix;
+    float c0, c1;               // lerp's coefficients: (float)(1 - mix), (float)mix
+};
+// The kernel's argument block by (SC, MX). A trait with plain specialisations, not a conditional over
+// an expression: the kernel's mangled name carries its parameter type as written, and the host and
+// device passes must agree on it symbol for symbol.
+template <bool SC, int MX> struct ListArgsSel { using type = ListArgsMix; };
+template <> struct ListArgsSel<false, 0> { using type = ListArgs; };
+template <> struct ListArgsSel<true, 0> { using type = ListArgsScaled; };
+template <bool SC, int MX>
+using ListArgsOf = typename ListArgsSel<SC, MX>::type;
 
 // SC: grad = round_g(-acc * L.grad_scale) (edt_outer_step_list_scaled), outer_elems' SC branch.
-template <int GDT, int WDT, int KC, int DIV, bool SC, class LA>
+// MX: the merge into L.live (edt_outer_step_list_mix), outer_elems' MX branch.
+template <int GDT, int WDT, int KC, int DIV, bool SC, int MX, class LA>
 __device__ __forceinline__ void outer_list_chunk(const LA& L, const uint64_t* prefix, uint64_t b) {
     uint64_t lo = 0, hi = L.T;                       // last t with prefix[t] <= b
     while (hi - lo > 1) {
@@ -185,9 +254,16 @@ __device__ __forceinline__ void outer_list_chunk(const LA& L, const uint64_t* pr
     const uint64_t n = nf & ~kVecFlag;
     const uint64_t c0 = (b - prefix[t]) * kListChunk;
     const uint64_t c1 = c0 + kListChunk < n ? c0 + kListChunk : n;
-    using TA = std::conditional_t<SC, TensorArgsScaled, TensorArgs>;
+    static_assert(!(SC && MX != MX_NONE), "a clipped step merges in a pass of its own");
+    using TA = std::conditional_t<MX != MX_NONE, TensorArgsMix, std::conditional_t<SC, TensorArgsScaled, TensorArgs>>;
     TA a;
     if constexpr (SC) a.grad_scale = L.grad_scale;
+    if constexpr (MX != MX_NONE) {
+        a.live = L.live;
+        a.nmix = L.nmix;
+        a.c0 = L.c0;
+        a.c1 = L.c1;
+    }
     a.theta = L.theta[t];
     a.mom = L.sgd.use_momentum ? L.mom[t] : nullptr;
     a.acc_out = nullptr;
@@ -208,26 +284,26 @@ __device__ __forceinline__ void outer_list_chunk(const LA& L, const uint64_t* pr
         constexpr uint64_t tile = (uint64_t)kBlock * kVec;
         const uint64_t vend = c0 + (c1 - c0) / tile * tile;
         for (uint64_t i = c0 + 4ull * threadIdx.x; i < vend; i += tile)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec, TA, 4 * kBlock, false, SC>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec, TA, 4 * kBlock, false, SC, MX>(a, i);
         for (uint64_t i = vend + threadIdx.x; i < c1; i += kBlock)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC, MX>(a, i);
     } else if (nf & kVecFlag) {
         const uint64_t vend = c0 + (c1 - c0) / kVec * kVec;
         for (uint64_t i = c0 + (uint64_t)threadIdx.x * kVec; i < vend; i += (uint64_t)kBlock * kVec)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec, TA, 4, false, SC>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, kVec, TA, 4, false, SC, MX>(a, i);
         const uint64_t i = vend + threadIdx.x;
-        if (i < c1) outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC>(a, i);
+        if (i < c1) outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC, MX>(a, i);
     } else {
         for (uint64_t i = c0 + threadIdx.x; i < c1; i += kBlock)
-            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC>(a, i);
+            outer_elems<GDT, WDT, KC, DIV, MODE_FUSED, 1, TA, 4, false, SC, MX>(a, i);
     }
 }
 
 // LDS = true: the chunk prefix sums are staged in LDS once per workgroup (dynamic shared
 // memory, (T + 1) x 8 bytes), so the per-chunk tensor search costs LDS reads, not a chain of
 // dependent global loads; LDS = false (very long tensor lists) searches the global table.
-template <int GDT, int WDT, int KC, int DIV, bool LDS, bool SC = false>
-__global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_list_kernel(std::conditional_t<SC, ListArgsScaled, ListArgs> L) {
+template <int GDT, int WDT, int KC, int DIV, bool LDS, bool SC = false, int MX = MX_NONE>
+__global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_list_kernel(ListArgsOf<SC, MX> L) {
     extern __shared__ uint64_t s_prefix[];
     const uint64_t* prefix = L.prefix;
     if constexpr (LDS) {
@@ -235,7 +311,7 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_list_kernel(std::
         __syncthreads();
         prefix = s_prefix;
     }
-    for (uint64_t b = blockIdx.x; b < L.chunks; b += gridDim.x) outer_list_chunk<GDT, WDT, KC, DIV, SC>(L, prefix, b);
+    for (uint64_t b = blockIdx.x; b < L.chunks; b += gridDim.x) outer_list_chunk<GDT, WDT, KC, DIV, SC, MX>(L, prefix, b);
 }
 
 // SGD from N per-rank fp32 partial sums of the same shard, summed in rank order (the sharded
@@ -370,6 +446,25 @@ int launch_list(int gdt, int wdt, const LA& L, bool div_exact, unsigned grid, hi
     });
 }
 
+// The mixing list step: mx is MX_BLEND, MX_HELD (the host has checked KC > 0 for it) or MX_COPY.
+int launch_list_mix(int gdt, int wdt, const ListArgsMix& L, bool div_exact, int mx, unsigned grid, hipStream_t s) {
+    const bool lds = L.T <= kListLdsMaxTensors;
+    const size_t shm = lds ? (size_t)(L.T + 1) * sizeof(uint64_t) : 0;
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_kc_div<KC_FUSED>(L.K, div_exact, [&](auto KC, auto DIV) {
+            return with_bool(lds, [&](auto LDS) {
+                constexpr int GD = decltype(G)::value, WD = decltype(W)::value, KCV = decltype(KC)::value,
+                              DV = decltype(DIV)::value;
+                constexpr bool LD = decltype(LDS)::value;
+                if (mx == MX_COPY) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_COPY><<<grid, kBlock, shm, s>>>(L);
+                else if (mx == MX_BLEND) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_BLEND><<<grid, kBlock, shm, s>>>(L);
+                else if constexpr (KCV > 0) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_HELD><<<grid, kBlock, shm, s>>>(L);
+                else return fail(EDT_ERR_ARG, "the held merge needs a compile-time worker count");
+                return check_launch("outer_list_kernel (mix)");
+            });
+        });
+    });
+}
 
 int fill_outer(OuterArgs& a, const void* theta, const void* const* theta_k, int K, int K_total, uint64_t n) {
     memset(&a, 0, sizeof(a));
@@ -574,19 +669,81 @@ uint64_t edt_outer_list_workspace_bytes(int T, int K) {
     return (uint64_t)(5 * (uint64_t)T + 1 + (uint64_t)K * T) * sizeof(uint64_t);
 }
 
+uint64_t edt_outer_list_mix_workspace_bytes(int T, int K, int nmix) {
+    if (T < 0 || K < 1 || nmix < 1) return 0;
+    return edt_outer_list_workspace_bytes(T, K) + (uint64_t)nmix * T * sizeof(uint64_t);
+}
+
 }   // extern "C"
 
-// SC: the scaled entry (grad_scale checked first, so a refused call writes nothing).
+// edt_outer_step_list_mix's merge: the destinations and the weight of theta_new in them
+struct MixSpec {
+    void* const* live;
+    int nmix;
+    double mix;
+};
+
+// The aliasing rule of the mixing step over its non-empty runs: live[j][r] may be exactly
+// theta_k[j][r] (same pointer, hence the same elements in the same thread); any other overlap of a
+// destination with theta, the momentum, a worker or another destination is refused. `held` is set
+// when every destination is its worker and nmix == K. One sort of the byte ranges, then a sweep.
+static int check_mix_ranges(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
+                            void* const* momentum_t, bool use_momentum, const uint64_t* numel, int T,
+                            const MixSpec& mx, bool& held) {
+    struct Range {
+        uintptr_t lo, hi;
+        int live;            // a destination (written in the worker dtype)
+    };
+    const uint64_t bg = gdt == EDT_BF16 ? 2 : 4, bw = wdt == EDT_BF16 ? 2 : 4;
+    thread_local std::vector<Range> rs;
+    rs.clear();
+    held = mx.nmix == K;
+    auto push = [&](const void* p, uint64_t bytes, int live) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+        rs.push_back({lo, lo + bytes, live});
+    };
+    for (int t = 0; t < T; ++t) {
+        const uint64_t n = numel[t];
+        if (!n) continue;
+        push(theta_t[t], n * bg, 0);
+        if (use_momentum) push(momentum_t[t], n * bg, 0);
+        for (int j = 0; j < mx.nmix; ++j) push(mx.live[(uint64_t)j * T + t], n * bw, 1);
+        for (int k = 0; k < K; ++k) {
+            const void* w = theta_k[(uint64_t)k * T + t];
+            if (k < mx.nmix && w == mx.live[(uint64_t)k * T + t]) continue;      // the allowed alias: one range
+            held = false;
+            push(w, n * bw, 0);
+        }
+    }
+    std::sort(rs.begin(), rs.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
+    uintptr_t end_any = 0, end_live = 0;      // furthest end so far: of any range, of a destination
+    for (const Range& r : rs) {
+        if (r.lo < (r.live ? end_any : end_live))
+            return fail(EDT_ERR_ARG, "a merge destination overlaps another operand (only live[j] == theta_k[j] may alias)");
+        if (r.hi > end_any) end_any = r.hi;
+        if (r.live && r.hi > end_live) end_live = r.hi;
+    }
+    return EDT_OK;
+}
+
+// SC: the scaled entry (grad_scale checked first, so a refused call writes nothing). mx: the mixing
+// entry's merge (null: none); its table trails the list step's in the workspace.
 template <bool SC>
 static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
                                 void* const* momentum_t, int has_momentum, const uint64_t* numel, int T,
                                 double lr, double momentum_coef, int nesterov, const uint8_t* tail,
                                 const uint64_t* tail_off, float grad_scale, void* workspace, uint64_t workspace_bytes,
-                                void* stream) {
+                                void* stream, const MixSpec* mx = nullptr) {
     g_err[0] = 0;
     if (!valid_pair(gdt, wdt)) return fail(EDT_ERR_ARG, "unsupported dtype pair (gdt/wdt)");
     if constexpr (SC)
         if (int rc = check_grad_scale(grad_scale)) return rc;
+    if (mx) {
+        if (!(mx->mix > 0.0 && mx->mix <= 1.0))                 // NaN fails both comparisons
+            return fail(EDT_ERR_ARG, "mix %g outside (0, 1]", mx->mix);
+        if (mx->nmix < 1 || mx->nmix > EDT_MAX_WORKERS)
+            return fail(EDT_ERR_ARG, "merge destination count %d out of range [1, %d]", mx->nmix, EDT_MAX_WORKERS);
+    }
     if (K < 1 || K > EDT_MAX_WORKERS)
         return fail(EDT_ERR_ARG, "worker count %d out of range [1, %d]", K, EDT_MAX_WORKERS);
     if (T < 0) return fail(EDT_ERR_ARG, "tensor count %d < 0", T);
@@ -594,12 +751,13 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     if (!theta_t || !theta_k || !numel) return fail(EDT_ERR_ARG, "null tensor table");
     const SgdScalars sg = make_sgd(gdt, lr, momentum_coef, has_momentum, nesterov);
     if (sg.use_momentum && !momentum_t) return fail(EDT_ERR_ARG, "momentum table is null");
-    const uint64_t need = edt_outer_list_workspace_bytes(T, K);
+    if (mx && !mx->live) return fail(EDT_ERR_ARG, "live is null");
+    const uint64_t need = mx ? edt_outer_list_mix_workspace_bytes(T, K, mx->nmix) : edt_outer_list_workspace_bytes(T, K);
     if (!workspace || workspace_bytes < need)
         return fail(EDT_ERR_ARG, "workspace of %llu bytes needed", (unsigned long long)need);
     if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(EDT_ERR_ARG, "workspace must be 8-byte aligned");
     if (tail && (gdt != EDT_BF16 || !tail_off)) return fail(EDT_ERR_ARG, "tail bits need a bf16 master and byte offsets");
-    // table: prefix[T+1] | numel[T] | theta[T] | mom[T] | w[K*T] | tail_off[T]   (all 8-byte words)
+    // table: prefix[T+1] | numel[T] | theta[T] | mom[T] | w[K*T] | tail_off[T] | live[nmix*T] (mx)   (all 8-byte words)
     thread_local std::vector<uint64_t> h;
     h.assign(need / sizeof(uint64_t), 0);
     uint64_t* prefix = h.data();
@@ -608,6 +766,7 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     uint64_t* pmo = pth + T;
     uint64_t* pw = pmo + T;
     uint64_t* ptail = pw + (uint64_t)K * T;
+    uint64_t* plive = ptail + T;
     if (tail)
         for (int t = 0; t < T; ++t) ptail[t] = tail_off[t];
     for (int t = 0; t < T; ++t) {
@@ -626,16 +785,29 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
                 if (!p) return fail(EDT_ERR_ARG, "theta_k[%d][%d] is null", k, t);
                 vec = vec && aligned16(p);
             }
+            if (mx)
+                for (int j = 0; j < mx->nmix; ++j) {
+                    const void* p = mx->live[(uint64_t)j * T + t];
+                    if (!p) return fail(EDT_ERR_ARG, "live[%d][%d] is null", j, t);
+                    vec = vec && aligned16(p);
+                }
         }
         prefix[t + 1] = prefix[t] + (n + kListChunk - 1) / kListChunk;
         nflag[t] = n | (vec ? kVecFlag : 0);
         pth[t] = reinterpret_cast<uintptr_t>(theta_t[t]);
         pmo[t] = sg.use_momentum ? reinterpret_cast<uintptr_t>(momentum_t[t]) : 0;
         for (int k = 0; k < K; ++k) pw[(uint64_t)k * T + t] = reinterpret_cast<uintptr_t>(theta_k[(uint64_t)k * T + t]);
+        if (mx)
+            for (int j = 0; j < mx->nmix; ++j)
+                plive[(uint64_t)j * T + t] = reinterpret_cast<uintptr_t>(mx->live[(uint64_t)j * T + t]);
     }
     const uint64_t chunks = prefix[T];
     if (chunks == 0) return EDT_OK;
     if (chunks > 0x7fffffffull) return fail(EDT_ERR_ARG, "too many elements for one launch");
+    bool held = false;
+    if (mx)
+        if (int rc = check_mix_ranges(theta_t, gdt, theta_k, wdt, K, momentum_t, sg.use_momentum != 0, numel, T, *mx, held))
+            return rc;
     hipStream_t st = (hipStream_t)stream;
     // pageable source, overwritten by this thread's next call: the runtime has read it when
     // hipMemcpyAsync returns and the copy is stream-ordered on the device — pinned by
@@ -643,7 +815,7 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     hipError_t e = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "tensor table upload failed: %s", hipGetErrorString(e));
     const uint64_t* d = static_cast<const uint64_t*>(workspace);
-    std::conditional_t<SC, ListArgsScaled, ListArgs> L;
+    std::conditional_t<SC, ListArgsScaled, ListArgsMix> L;      // the plain entries launch its ListArgs base
     if constexpr (SC) L.grad_scale = grad_scale;
     L.prefix = d;
     L.numel = d + T + 1;
@@ -659,7 +831,20 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     L.tail = tail;
     L.tail_off = d + 4 * (uint64_t)T + 1 + (uint64_t)K * T;
     const unsigned grid = chunks > kMaxBlocks ? (unsigned)kMaxBlocks : (unsigned)chunks;   // grid-stride
-    return launch_list<SC>(gdt, wdt, L, !is_pow2(K), grid, st);
+    if constexpr (!SC) {
+        if (mx) {
+            L.live = reinterpret_cast<void* const*>(L.tail_off + T);
+            L.nmix = mx->nmix;
+            L.c0 = (float)(1.0 - mx->mix);                      // as edt_lerp forms them
+            L.c1 = (float)mx->mix;
+            const bool kc = K == 1 || K == 2 || K == 3 || K == 4 || K == 8;       // with_kc_div<KC_FUSED>'s bodies
+            const int mode = mx->mix == 1.0 ? MX_COPY : held && kc ? MX_HELD : MX_BLEND;
+            return launch_list_mix(gdt, wdt, L, !is_pow2(K), mode, grid, st);
+        }
+        return launch_list<SC>(gdt, wdt, static_cast<const ListArgs&>(L), !is_pow2(K), grid, st);
+    } else {
+        return launch_list<SC>(gdt, wdt, L, !is_pow2(K), grid, st);
+    }
 }
 
 // The two sharded SGD entries and their scaled forms (SC: the clip coefficient is checked first,
@@ -749,6 +934,16 @@ int edt_outer_step_list_scaled(void* const* theta_t, int gdt, const void* const*
     return outer_step_list_impl<true>(theta_t, gdt, theta_k, wdt, K, momentum_t, has_momentum, numel, T, lr,
                                       momentum_coef, nesterov, tail_bits, tail_byte_offset, grad_scale, workspace,
                                       workspace_bytes, stream);
+}
+
+int edt_outer_step_list_mix(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
+                            void* const* momentum_t, int has_momentum, const uint64_t* numel, int T,
+                            double lr, double momentum_coef, int nesterov, void* const* live, int nmix,
+                            double mix, void* workspace, uint64_t workspace_bytes, void* stream) {
+    const MixSpec mx = {live, nmix, mix};
+    return outer_step_list_impl<false>(theta_t, gdt, theta_k, wdt, K, momentum_t, has_momentum, numel, T, lr,
+                                       momentum_coef, nesterov, nullptr, nullptr, 1.f, workspace, workspace_bytes, stream,
+                                       &mx);
 }
 
 int edt_delta_partial(const void* theta_g, int gdt, const void* const* theta_k, int wdt, int K_local,

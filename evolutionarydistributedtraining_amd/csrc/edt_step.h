@@ -54,10 +54,18 @@ __device__ __forceinline__ void for_whole_waves(uint64_t n, F&& f) {
 // The loop over k (KC unrolled, else `unroll 4`) stays with the two callers: a loop counter declared
 // in an inlined callee is promoted to a register before the caller's acc, the loop's phi order
 // flips, and the generic-K kernels' register allocation moves with it (spills, lost occupancy).
-template <int GDT, int WDT, int DIV, int N, int H2, bool ROUND_ACC, class A>
-__device__ __forceinline__ void add_delta(const A& a, int k, const float (&g)[N], float (&acc)[N], uint64_t i) {
+// raw: at most one float[N], which receives w_k as loaded (the fused merge's aliased form blends
+// into the value the delta used without loading it again); without it nothing is emitted.
+template <int GDT, int WDT, int DIV, int N, int H2, bool ROUND_ACC, class A, class... R>
+__device__ __forceinline__ void add_delta(const A& a, int k, const float (&g)[N], float (&acc)[N], uint64_t i,
+                                          R&... raw) {
+    static_assert(sizeof...(R) <= 1, "at most one copy of the worker's values");
     float w[N];
     ld<WDT, N, nt_worker_loads<WDT, H2>(), H2>(a.wp(k), i, w);
+    if constexpr (sizeof...(R) == 1) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) ((raw[j] = w[j]), ...);
+    }
 #pragma unroll
     for (int j = 0; j < N; ++j) w[j] = w[j] - g[j];              // trained - base
     rnd<GDT>(w);

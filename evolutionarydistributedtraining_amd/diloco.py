@@ -22,6 +22,7 @@ from . import ops
 from ._lib import EDT_MAX_WORKERS as L_MAX, EdtError
 from .guard import NonFiniteWorkers, OuterGuard, clip_coefficient, guard_decision, stats_totals  # re-exported
 from .guard import fold_remeasured, report
+from .fragments import FragmentPlan
 from .params import ParamArena, ParamLayout, flat_view, pack, unpack_
 from .tracing import traced
 
@@ -59,6 +60,28 @@ class OuterState:
         self.place_momentum = int(place_momentum)
         self.placement: dict | None = None
         self.last_stats: dict | None = None         # the last guarded step's report (OuterGuard)
+        # fragment-wise stepping (step_fragment, outer_step_fragment): one flag and one count per
+        # fragment of the attached plan; a fragment's first step takes buf = grad for its tensors only
+        self.fragment_has_momentum: list[bool] | None = None
+        self.fragment_steps: list[int] | None = None
+        self.fragments: "FragmentPlan | None" = None
+
+    def attach_fragments(self, plan: "FragmentPlan") -> None:
+        """Start (or keep) the per-fragment flags for `plan`: a state that has stepped as a whole
+        carries its momentum into every fragment."""
+        P = len(plan)
+        self.fragments = plan
+        if self.fragment_has_momentum is None or len(self.fragment_has_momentum) != P:
+            self.fragment_has_momentum = [bool(self.has_momentum)] * P
+            self.fragment_steps = [0] * P
+
+    def fragment_stepped(self, p: int, with_momentum: bool) -> None:
+        """Fragment p has taken a step: its flag, the counts, and has_momentum once every one has."""
+        if with_momentum:
+            self.fragment_has_momentum[p] = True
+            self.has_momentum = all(self.fragment_has_momentum)
+        self.fragment_steps[p] += 1
+        self.steps += 1
 
     def buffer_for(self, theta: torch.Tensor, numel: int | None = None) -> torch.Tensor:
         """The flat momentum for parameters like `theta` (numel: total count when theta is
@@ -76,38 +99,74 @@ class OuterState:
         return self.momentum
 
     # --- torch.optim.SGD state_dict interop (index-keyed, as load_state_dict carries it) ---
-    def state_dict(self, layout: ParamLayout) -> dict:
+    def state_dict(self, layout: ParamLayout, fragments: "FragmentPlan | None" = None) -> dict:
+        """A fragment-wise run whose fragments have not all stepped yet emits `momentum_buffer` only
+        for the tensors of those that have (torch's own shape for a state in which some parameters
+        have never had a gradient). fragments: the plan, when none is attached to the state."""
         state = {}
+        fragments = fragments or self.fragments
         if self.momentum is not None and self.has_momentum:
             for i, v in enumerate(layout.views(self.momentum)):
                 state[i] = {"momentum_buffer": v.detach().to("cpu", copy=True)}
+        elif self.momentum is not None and self.fragment_has_momentum is not None and any(self.fragment_has_momentum):
+            if fragments is None or len(fragments) != len(self.fragment_has_momentum):
+                raise EdtError("a partly stepped fragment state needs its FragmentPlan (state_dict(layout, fragments=plan))")
+            views = layout.views(self.momentum)
+            for p, has in enumerate(self.fragment_has_momentum):
+                for i in (fragments.tensors(p) if has else []):
+                    state[i] = {"momentum_buffer": views[i].detach().to("cpu", copy=True)}
+            state = dict(sorted(state.items()))
         group = dict(lr=self.hparams["lr"], momentum=self.hparams["momentum"], dampening=0,
                      weight_decay=0, nesterov=self.hparams["nesterov"], maximize=False,
                      foreach=None, differentiable=False, fused=None,
                      params=list(range(len(layout))))
         return {"state": state, "param_groups": [group]}
 
-    def load_state_dict(self, sd: dict, layout: ParamLayout, dtype: torch.dtype, device) -> None:
+    def load_state_dict(self, sd: dict, layout: ParamLayout, dtype: torch.dtype, device,
+                        fragments: "FragmentPlan | None" = None) -> None:
+        """fragments: accept a partial state exactly when the buffers present are whole fragments
+        of the plan; the other fragments' momentum is zero-filled and their flags stay clear."""
         group = sd["param_groups"][0]
         self.hparams = dict(lr=group["lr"], momentum=group["momentum"], nesterov=group["nesterov"])
         bufs = [sd["state"].get(i, {}).get("momentum_buffer") for i in range(len(layout))]
+        self.fragment_has_momentum = self.fragment_steps = self.fragments = None
         if all(b is None for b in bufs):
             self.momentum, self.has_momentum = None, False
+            if fragments is not None:
+                self.attach_fragments(fragments)
             return
         if any(b is None for b in bufs):
-            raise EdtError("partial momentum state is not supported (every parameter needs a buffer)")
+            if fragments is None:
+                raise EdtError("partial momentum state is not supported (every parameter needs a buffer)")
+            if len(fragments.layout) != len(layout):
+                raise EdtError("the fragment plan does not match the layout")
+            present = [[bufs[i] is not None for i in fragments.tensors(p)] for p in range(len(fragments))]
+            if any(any(f) and not all(f) for f in present):
+                raise EdtError("partial momentum state must hold whole fragments of the plan")
+            flat = torch.zeros(layout.total, dtype=dtype, device=device)
+            for v, b in zip(layout.views(flat), bufs):
+                if b is not None:
+                    v.copy_(b)
+            self.momentum, self.has_momentum = flat, False
+            self.fragments = fragments
+            self.fragment_has_momentum = [bool(f) and all(f) for f in present]
+            self.fragment_steps = [0] * len(fragments)
+            return
         flat = torch.empty(layout.total, dtype=dtype, device=device)
         for v, b in zip(layout.views(flat), bufs):
             v.copy_(b)
         self.momentum, self.has_momentum = flat, True
+        if fragments is not None:
+            self.attach_fragments(fragments)
 
     def save(self, path: str, layout: ParamLayout) -> None:
         torch.save(self.state_dict(layout), path)
 
     @classmethod
-    def load(cls, path: str, layout: ParamLayout, dtype, device) -> "OuterState":
+    def load(cls, path: str, layout: ParamLayout, dtype, device, fragments: "FragmentPlan | None" = None) -> "OuterState":
         st = cls()
-        st.load_state_dict(torch.load(path, map_location="cpu", weights_only=True), layout, dtype, device)
+        st.load_state_dict(torch.load(path, map_location="cpu", weights_only=True), layout, dtype, device,
+                           fragments=fragments)
         return st
 
 
@@ -275,6 +334,123 @@ def _step_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]], st
     state.steps += 1
 
 
+def _merge_unfused(thetas, live, mix: float, scratch: torch.Tensor) -> None:
+    """The merge as passes of its own, after a step that has no fused one (the clipped step, as the
+    clipped broadcast): theta_new rounded to the worker dtype into `scratch` (edt_broadcast_theta per
+    run), then `lerp` into every destination; mix == 1 broadcasts straight into the destinations."""
+    off = 0
+    for r, th in enumerate(thetas):
+        n = th.numel()
+        if n == 0:
+            continue
+        dst = [l[r] for l in live]
+        if mix == 1.0:
+            ops.broadcast_theta(th, dst)
+        else:
+            v = scratch[off:off + n]
+            ops.broadcast_theta(th, [v])
+            for d in dst:
+                ops.lerp(mix, d, v, out=d)
+        off += n
+
+
+def _step_fragment(thetas, deltas, live, moms, state: OuterState, p: int, lr: float, momentum: float,
+                   nesterov: bool, mix: float, guard: OuterGuard | None) -> None:
+    """One fragment's outer step over its runs where they lie. thetas / moms: the R run views of
+    theta and of the momentum (moms None without momentum); deltas: K lists of R runs the
+    pseudo-gradient is taken from (the live workers or snapshots); live: the merge destinations
+    (nmix lists of R runs), None for the plain fragment step."""
+    check_sgd_hparams(lr, momentum, nesterov)
+    mix = float(mix)
+    if not 0.0 < mix <= 1.0:
+        raise EdtError(f"mix {mix} outside (0, 1]")
+    if len(deltas) > L_MAX or (live is not None and len(live) > L_MAX):
+        raise EdtError(f"a fragment step takes at most {L_MAX} workers")
+    clip = 1.0
+    if guard is not None and thetas:            # before anything is written
+        plans = state.__dict__.setdefault("_fragment_stats_plans", {})
+        state._stats_list_plan = plans.get(p)   # the chunk plan is per fragment: its runs' sizes
+        try:
+            survivors, clip = _guard_pass_list(thetas, deltas, state, guard)
+        finally:
+            plans[p] = state._stats_list_plan
+        if live is not None and len(survivors) < len(deltas) and len(live) == len(deltas):
+            # a dropped worker is still a destination; the survivors' stay at their delta's index,
+            # where a destination may alias its worker
+            gone = [k for k in range(len(deltas)) if k not in survivors]
+            live = [live[k] for k in list(survivors) + gone]
+        deltas = [deltas[k] for k in survivors]
+    state.hparams = dict(lr=lr, momentum=momentum, nesterov=nesterov)
+    has = state.fragment_has_momentum[p] if momentum != 0 else False
+    if live is None:
+        if clip != 1.0:
+            ops.outer_step_list_scaled(thetas, deltas, moms, has, lr, momentum, nesterov, clip)
+        else:
+            ops.outer_step_list(thetas, deltas, moms, has, lr, momentum, nesterov)
+    elif clip != 1.0:                           # clipped: the scaled form has no fused merge
+        ops.outer_step_list_scaled(thetas, deltas, moms, has, lr, momentum, nesterov, clip)
+        scratch = None
+        if mix != 1.0:
+            scratch = torch.empty(sum(t.numel() for t in thetas), dtype=live[0][0].dtype, device=thetas[0].device)
+        _merge_unfused(thetas, live, mix, scratch)
+    else:
+        ops.outer_step_list_mix(thetas, deltas, moms, has, lr, momentum, nesterov, live, mix)
+    state.fragment_stepped(p, momentum != 0)
+
+
+def outer_step_fragment(base_params, worker_params, state: OuterState | None, plan: FragmentPlan, p: int,
+                        mix: float = 1.0, snapshot_params=None, live_params=None, lr: float = 0.7,
+                        momentum: float = 0.9, nesterov: bool = True, guard: OuterGuard | None = None,
+                        merge: bool = True) -> OuterState:
+    """The drop-in's fragment step (Streaming DiLoCo) on `parameters()` lists: fragment p of `plan`
+    is stepped, its tensors passed where they lie, one run per tensor, nothing packed; every other
+    tensor of the base model, of the momentum and of the workers is left as it is.
+    worker_params: K lists of the replicas' parameters. snapshot_params: K lists the pseudo-gradient
+    is taken from instead (copies of the fragment's tensors made some inner steps earlier; default:
+    the workers as they are). live_params: the lists the merge goes into (default: worker_params):
+    every tensor w of the fragment becomes lerp(mix, w, theta_new) in the worker dtype; merge=False
+    steps theta and the momentum only. The three take whole parameter lists or the fragment's
+    tensors alone (in `plan.tensors(p)` order). state carries the momentum and the per-fragment flags:
+    a fragment's first step takes buf = grad for its own tensors."""
+    state = state or OuterState()
+    base_params = list(base_params)
+    if len(base_params) != len(plan.layout) or [q.numel() for q in base_params] != plan.layout.numels:
+        raise EdtError("the base parameters do not match the fragment plan's layout")
+    idx = [i for i in plan.tensors(p) if plan.layout.numels[i]]
+
+    def pick(lists, what):
+        out = []
+        for w in lists:
+            w = list(w)
+            if len(w) == len(base_params):
+                out.append([w[i] for i in idx])
+            elif len(w) == len(plan.tensors(p)):
+                out.append([t for t, i in zip(w, plan.tensors(p)) if plan.layout.numels[i]])
+            else:
+                raise EdtError(f"{what}: a whole parameter list or the fragment's tensors")
+        return out
+
+    if not worker_params:
+        raise EdtError("no trained models")
+    workers = pick(worker_params, "worker_params")
+    deltas = workers if snapshot_params is None else pick(snapshot_params, "snapshot_params")
+    live = None
+    if merge:
+        live = workers if live_params is None else pick(live_params, "live_params")
+    with torch.no_grad():
+        thetas = [base_params[i].detach().view(-1) for i in idx]
+        flat1 = lambda lists: [[t.detach().view(-1) for t in l] for l in lists]
+        state.attach_fragments(plan)
+        moms = None
+        if momentum != 0:
+            flat = state.buffer_for(base_params[0], plan.layout.total)
+            moms = [flat[plan.layout.offsets[i]:plan.layout.offsets[i] + plan.layout.numels[i]] for i in idx]
+        deltas_f = flat1(deltas)
+        live_f = None if live is None else (deltas_f if live is deltas else flat1(live))
+        _step_fragment(thetas, deltas_f, live_f, moms, state, p, lr, momentum, nesterov, mix, guard)
+    return state
+
+
 def outer_step(base_params, worker_params, state: OuterState | None = None, lr: float = 0.7,
                momentum: float = 0.9, nesterov: bool = True, cpu_tails: tuple[int, int] | None = None,
                guard: OuterGuard | None = None) -> OuterState:
@@ -346,9 +522,18 @@ class OuterSync:
 
     def __init__(self, theta: ParamArena, workers: list[ParamArena], lr: float = 0.7,
                  momentum: float = 0.9, nesterov: bool = True, state: OuterState | None = None,
-                 cpu_tails: tuple[int, int] | None = None, guard: OuterGuard | None = None):
+                 cpu_tails: tuple[int, int] | None = None, guard: OuterGuard | None = None,
+                 fragments: FragmentPlan | None = None):
         if guard is not None and len(workers) > L_MAX:
             raise EdtError(f"a guarded step takes at most {L_MAX} workers")
+        if fragments is not None:
+            if cpu_tails is not None:
+                raise EdtError("fragment-wise stepping has no scalar-tail emulation (cpu_tails)")
+            if len(workers) > L_MAX:
+                raise EdtError(f"a fragment step takes at most {L_MAX} workers")
+            if fragments.layout.numels != theta.layout.numels:
+                raise EdtError("the fragment plan does not match the arena's layout")
+        self.fragments = fragments
         self.guard = guard
         self.theta = theta
         self.workers = workers
@@ -356,6 +541,8 @@ class OuterSync:
         self.state = state or OuterState()
         # (Vec::size(), threads) of the reference's host: its bf16 scalar tails (outer_step's doc)
         self.tail_bits = _tail_bits(cpu_tails, theta.layout.numels, theta.flat.device)
+        if fragments is not None:
+            self.state.attach_fragments(fragments)
 
     @traced("edt/OuterSync.step")
     def step(self, broadcast: bool = False) -> None:
@@ -366,9 +553,68 @@ class OuterSync:
         broadcast then still reaches every worker arena, a dropped one included, so it rejoins
         from the new theta; after a clipped step it is a pass of its own (edt_broadcast_theta)."""
         ws = [w.flat for w in self.workers]
+        flags = self.state.fragment_has_momentum if self.fragments is not None else None
+        if flags and self.momentum != 0 and any(flags) and not all(flags):
+            raise EdtError("a whole step needs every fragment's momentum or none: some fragments have stepped, some not")
         _step_flat(self.theta.flat, ws, self.state, self.lr, self.momentum, self.nesterov,
                    ws if broadcast else None, tail_bits=self.tail_bits, guard=self.guard,
                    numels=self.theta.layout.numels)
+        if flags and self.momentum != 0:
+            self.state.fragment_has_momentum = [True] * len(flags)
+
+    def capture_fragment(self, p: int, out: list[torch.Tensor] | None = None) -> list[torch.Tensor]:
+        """Snapshots of fragment p of every worker arena, for a later `step_fragment(p,
+        snapshots=...)`: K flat buffers of the fragment's size in the workers' dtype, the fragment's
+        runs back to back (one copy_ per run). out: buffers to reuse."""
+        plan = self._plan()
+        n = plan.numel(p)
+        if out is None:
+            out = [torch.empty(n, dtype=w.flat.dtype, device=w.flat.device) for w in self.workers]
+        if len(out) != len(self.workers) or any(o.numel() != n or o.dtype != w.flat.dtype
+                                                for o, w in zip(out, self.workers)):
+            raise EdtError("snapshots: one flat buffer of the fragment's size and the workers' dtype per worker")
+        for o, w in zip(out, self.workers):
+            for dst, src in zip(plan.snapshot_views(p, o), plan.views(p, w.flat)):
+                dst.copy_(src)
+        return out
+
+    def _plan(self) -> FragmentPlan:
+        if self.fragments is None:
+            raise EdtError("no FragmentPlan attached (OuterSync(..., fragments=plan))")
+        return self.fragments
+
+    @traced("edt/OuterSync.step_fragment")
+    def step_fragment(self, p: int, mix: float = 1.0, snapshots: list[torch.Tensor] | None = None,
+                      merge: bool = True) -> None:
+        """One outer step of fragment p alone (Streaming DiLoCo), over the run views of theta, the
+        momentum and the workers: nothing is packed, and no tensor outside the fragment is touched.
+        snapshots: K flat buffers of the fragment's size (`capture_fragment`) the pseudo-gradient is
+        taken from; None: the live worker arenas. The new theta then goes into every worker arena's
+        runs as a merge, w <- lerp(mix, w, theta_new) in the worker dtype (Streaming DiLoCo's alpha is
+        1 - mix; mix = 1 overwrites), in the step's own pass (edt_outer_step_list_mix); merge=False is
+        the plain fragment step (edt_outer_step_list). The momentum of a fragment advances only when
+        it is stepped, and its first step takes buf = grad for its own tensors.
+        With a guard the statistics, the screening and the clip are the fragment's own; a refusal
+        leaves theta, the momentum and every worker untouched, a dropped worker is still merged
+        into, and a clipped step merges in passes of its own (edt_broadcast_theta, then lerp)."""
+        plan = self._plan()
+        if not 0 <= p < len(plan):
+            raise EdtError(f"fragment {p} out of range [0, {len(plan)})")
+        self.state.attach_fragments(plan)
+        thetas = plan.views(p, self.theta.flat)
+        moms = plan.views(p, self.state.buffer_for(self.theta.flat)) if self.momentum != 0 else None
+        live = [plan.views(p, w.flat) for w in self.workers]
+        if snapshots is None:
+            deltas = live
+        else:
+            if len(snapshots) != len(self.workers):
+                raise EdtError("snapshots: one buffer per worker")
+            try:
+                deltas = [plan.snapshot_views(p, s) for s in snapshots]
+            except ValueError as e:
+                raise EdtError(str(e)) from None
+        _step_fragment(thetas, deltas, live if merge else None, moms, self.state, p, self.lr, self.momentum,
+                       self.nesterov, mix, self.guard)
 
     @property
     def last_stats(self) -> dict | None:
@@ -395,6 +641,8 @@ class OuterSync:
         the momentum placed inside each). The arenas are re-pointed at the chosen buffers with
         their contents unchanged; a module bound to an arena (params.bind_module_) must be bound
         again afterwards. With draws = 1 this is place_momentum."""
+        if self.fragments is not None:
+            raise EdtError("place_arenas moves the arenas: run it before a FragmentPlan is attached")
         if self.momentum == 0:
             return {"draws": [], "chosen_draw": None}
         from .placement import place_set

@@ -165,6 +165,85 @@ def outer_step_list_scaled(thetas: list[torch.Tensor], workers: list[list[torch.
     _outer_step_list(thetas, workers, momenta, has_momentum, lr, momentum_coef, nesterov, tails, float(grad_scale))
 
 
+def outer_step_list_mix(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]],
+                        momenta: list[torch.Tensor] | None, has_momentum: bool, lr: float,
+                        momentum_coef: float, nesterov: bool, live: list[list[torch.Tensor]], mix: float) -> None:
+    """`outer_step_list` over R runs fused with Streaming DiLoCo's worker merge
+    (edt_outer_step_list_mix), one launch: theta and the momentum are `outer_step_list`'s bit for bit
+    (workers: the delta workers, e.g. snapshots of a fragment), and every destination live[j][r]
+    (nmix lists of R tensors in the workers' dtype and the runs' sizes; nmix need not be K) becomes
+    `lerp(mix, live[j][r], theta_new.to(worker dtype))` in the worker dtype, bit for bit. Streaming
+    DiLoCo's alpha is 1 - mix; mix == 1.0 overwrites (the destination is not read: the list form's
+    fused broadcast). live[j][r] may be exactly workers[j][r]; any other overlap among the destinations,
+    the workers, theta and the momentum is refused, as is a mix outside (0, 1]: EdtError before
+    anything is launched."""
+    lib = L.lib()
+    T, K = len(thetas), len(workers)
+    live = [list(l) for l in live]
+    nmix = len(live)
+    if K == 0:
+        raise L.EdtError("no workers")
+    if K > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"tensor-list step takes at most {L.EDT_MAX_WORKERS} workers")
+    if not 1 <= nmix <= L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"the merge takes 1 to {L.EDT_MAX_WORKERS} destinations")
+    mix = float(mix)
+    if not 0.0 < mix <= 1.0:                     # NaN fails both comparisons
+        raise L.EdtError(f"mix {mix} outside (0, 1]")
+    if momentum_coef != 0 and momenta is None:
+        raise L.EdtError("momentum tensors are required when momentum != 0")
+    flat_w, numels, gdt, wdt = _check_list_operands(thetas, workers, momenta)
+    if any(len(l) != T for l in live):
+        raise L.EdtError("every merge destination needs one tensor per run")
+    if T == 0:
+        return
+    flat_l = [t for l in live for t in l]
+    dev = thetas[0].device
+    if not all([t.is_cuda and t.is_contiguous() and t.device == dev for t in flat_l]):
+        raise L.EdtError("merge destinations must be contiguous tensors on the operands' device")
+    if {t.dtype for t in flat_l} != {wdt} or any([t.numel() for t in l] != numels for l in live):
+        raise L.EdtError("merge destinations must have the workers' dtype and the runs' sizes")
+    _check_mix_aliasing(thetas, workers, momenta if momentum_coef != 0 else None, live, numels)
+    numel = (ctypes.c_uint64 * T)(*numels)
+    nbytes = lib.edt_outer_list_mix_workspace_bytes(T, K, nmix)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    P_ = ctypes.c_void_p
+    th_arr = (P_ * T)(*[t.data_ptr() for t in thetas])
+    w_arr = (P_ * len(flat_w))(*[t.data_ptr() for t in flat_w])
+    l_arr = (P_ * len(flat_l))(*[t.data_ptr() for t in flat_l])
+    m_arr = (P_ * T)(*[t.data_ptr() for t in momenta]) if momenta is not None else None
+    L.check(lib.edt_outer_step_list_mix(th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, m_arr, int(has_momentum),
+                                        numel, T, float(lr), float(momentum_coef), int(nesterov), l_arr, nmix, mix,
+                                        L.ptr(ws), nbytes, L.stream_ptr(dev)), "edt_outer_step_list_mix")
+
+
+def _check_mix_aliasing(thetas, workers, momenta, live, numels) -> None:
+    """The mixing step's aliasing rule from data_ptr ranges (what edt_outer_step_list_mix checks
+    again on the host side of the ABI): live[j][r] may be exactly workers[j][r]; any other overlap of a
+    destination with theta, the momentum, a worker or another destination is refused."""
+    rs = []                                      # (lo, hi, is a destination)
+    for r, n in enumerate(numels):
+        if n == 0:
+            continue
+        rs.append((thetas[r].data_ptr(), thetas[r].data_ptr() + n * thetas[r].element_size(), False))
+        if momenta is not None:
+            rs.append((momenta[r].data_ptr(), momenta[r].data_ptr() + n * momenta[r].element_size(), False))
+        for l in live:
+            rs.append((l[r].data_ptr(), l[r].data_ptr() + n * l[r].element_size(), True))
+        for k, w in enumerate(workers):
+            if k < len(live) and w[r].data_ptr() == live[k][r].data_ptr():
+                continue                         # the allowed alias: one range
+            rs.append((w[r].data_ptr(), w[r].data_ptr() + n * w[r].element_size(), False))
+    rs.sort(key=lambda x: x[0])
+    end_any = end_live = 0
+    for lo, hi, is_live in rs:
+        if lo < (end_any if is_live else end_live):
+            raise L.EdtError("a merge destination overlaps another operand (only live[j] is workers[j] may alias)")
+        end_any = max(end_any, hi)
+        if is_live:
+            end_live = max(end_live, hi)
+
+
 def _check_list_operands(thetas, workers, momenta) -> tuple:
     """The operand checks of the tensor-list entries: (flat worker list, sizes, theta's dtype, the
     workers' dtype). One comprehension per property over all T x (K + 2) tensors (the drop-in path

@@ -72,11 +72,15 @@ def inner_train(model, worker: int, gen: int, steps: int, device, lr: float = 3e
 
 
 def run(generations: int = 5, workers: int = 4, inner_steps: int = 20, device="cuda", seed: int = 0,
-        before_outer=None, after_outer=None, log=print, max_grad_norm=None, on_nonfinite=None):
+        before_outer=None, after_outer=None, log=print, max_grad_norm=None, on_nonfinite=None,
+        fragments: int = 0, mix: float = 0.5):
     """The simulation loop. before_outer(gen, base, replicas) / after_outer(gen, base, state) are
     hooks (the tests snapshot and check the outer step there). Returns the eval losses.
     max_grad_norm / on_nonfinite: run the outer step under a diloco.OuterGuard (off by default)
-    and log the pseudo-gradient's norm per outer step."""
+    and log the pseudo-gradient's norm per outer step.
+    fragments = P > 0: Streaming DiLoCo — the parameters are cut into P sequential fragments, each
+    outer step synchronises one of them, round robin, and the workers live on across outer steps:
+    the new fragment is merged into them, w <- lerp(mix, w, theta_new) (diloco.outer_step_fragment)."""
     from evolutionarydistributedtraining_amd import diloco
     guard = None
     if max_grad_norm is not None or on_nonfinite is not None:
@@ -86,18 +90,32 @@ def run(generations: int = 5, workers: int = 4, inner_steps: int = 20, device="c
     base = TinyLM().to(device)
     state = None
     evals = []
+    plan, replicas = None, []
+    if fragments:
+        from evolutionarydistributedtraining_amd import FragmentPlan, ParamLayout
+        plan = FragmentPlan.sequential(ParamLayout.of_module(base), fragments)
+        replicas = [copy.deepcopy(base) for _ in range(workers)]
     for gen in range(generations):
-        replicas = []
-        for k in range(workers):                     # every worker starts from the global model
+        if plan is not None:
+            for k, m in enumerate(replicas):             # the workers train on from where the merge left them
+                inner_train(m, k, gen, inner_steps, device)
+        else:
+            replicas = []
+        for k in range(workers if plan is None else 0):  # every worker starts from the global model
             m = copy.deepcopy(base)
             inner_train(m, k, gen, inner_steps, device)
             replicas.append(m)
         if before_outer:
             before_outer(gen, base, replicas)
         with torch.no_grad():
-            state = diloco.outer_step(list(base.parameters()), [list(m.parameters()) for m in replicas], state,
-                                      lr=0.7, momentum=0.9, nesterov=True,
-                                      **({"guard": guard} if guard is not None else {}))
+            if plan is not None:
+                state = diloco.outer_step_fragment(list(base.parameters()), [list(m.parameters()) for m in replicas],
+                                                   state, plan, gen % fragments, mix=mix, lr=0.7, momentum=0.9,
+                                                   nesterov=True, guard=guard)
+            else:
+                state = diloco.outer_step(list(base.parameters()), [list(m.parameters()) for m in replicas], state,
+                                          lr=0.7, momentum=0.9, nesterov=True,
+                                          **({"guard": guard} if guard is not None else {}))
         if after_outer:
             after_outer(gen, base, state)
         with torch.no_grad():
@@ -120,8 +138,13 @@ def main():
                     help="clip the outer pseudo-gradient to this 2-norm (diloco.OuterGuard)")
     ap.add_argument("--on-nonfinite", choices=("raise", "drop", "ignore"), default=None,
                     help="what a NaN / Inf worker does to the outer step (diloco.OuterGuard)")
+    ap.add_argument("--fragments", type=int, default=0,
+                    help="P > 0: synchronise one of P sequential fragments per outer step (Streaming DiLoCo)")
+    ap.add_argument("--mix", type=float, default=0.5,
+                    help="with --fragments: the weight of the new global fragment in every worker, in (0, 1]")
     a = ap.parse_args()
-    run(a.generations, a.workers, a.inner_steps, max_grad_norm=a.max_grad_norm, on_nonfinite=a.on_nonfinite)
+    run(a.generations, a.workers, a.inner_steps, max_grad_norm=a.max_grad_norm, on_nonfinite=a.on_nonfinite,
+        fragments=a.fragments, mix=a.mix)
 
 
 if __name__ == "__main__":

@@ -172,6 +172,31 @@ int edt_outer_step_list_scaled(void* const* theta_t, int gdt, const void* const*
                                const uint64_t* tail_byte_offset, float grad_scale, void* workspace,
                                uint64_t workspace_bytes, void* stream);
 
+/* edt_outer_step_list fused with Streaming DiLoCo's worker merge, over T runs (a run is one
+ * contiguous stretch per operand: a tensor, or a view into an arena). The step is
+ * edt_outer_step_list's, bit for bit, on the same runs: theta_k are the delta workers (usually
+ * snapshots of a fragment taken some inner steps earlier). In the same pass every merge destination
+ *   live[j * T + t], j < nmix   (host array of device pointers, worker dtype, numel[t] elements)
+ * moves towards v = round_w(theta_new), the value edt_outer_step_bcast stores, by edt_lerp's rule
+ * with t = mix in the worker dtype: c0 = (float)(1.0 - mix), c1 = (float)mix,
+ *   live = round_w(round_w(c0 * live) + round_w(c1 * v))
+ * i.e. edt_lerp(live, v, wdt, live, wdt, wdt, n, mix). Streaming DiLoCo's alpha is 1 - mix.
+ * mix == 1.0 is the overwrite: the destination is not read (NaN / Inf in it do not survive) and v is
+ * stored, as edt_outer_step_bcast does. mix must be finite and in (0, 1], 1 <= nmix <=
+ * EDT_MAX_WORKERS (nmix may differ from K), else EDT_ERR_ARG.
+ * Aliasing: live[j * T + t] may be exactly theta_k[j * T + t] (the worker is read before it is
+ * overwritten, element by element, by the same thread); any other overlap of a destination with
+ * theta, the momentum, a worker or another destination is EDT_ERR_ARG, nothing launched. When
+ * every destination is its worker and nmix == K in {1, 2, 3, 4, 8} the worker values the delta
+ * loaded are merged from registers. A run takes the vector body when all its K + 2 + nmix
+ * pointers are 16-byte aligned. The workspace (edt_outer_list_mix_workspace_bytes(T, K, nmix)) is
+ * edt_outer_step_list's with the destination table behind it. */
+uint64_t edt_outer_list_mix_workspace_bytes(int T, int K, int nmix);
+int edt_outer_step_list_mix(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
+                            void* const* momentum_t, int has_momentum, const uint64_t* numel, int T,
+                            double lr, double momentum, int nesterov, void* const* live, int nmix,
+                            double mix, void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* Tensor-list form of edt_delta_stats: the statistics of the step edt_outer_step_list would take
  * on T separate tensors, read where they lie (nothing is packed, nothing is written but `out` and
  * `workspace`).
