@@ -1,6 +1,7 @@
 // edt_common.h — what every kernel translation unit of libedt_sync.so shares: the build-time
 // tunables, vector types, bf16 rounding, the 8-element load/store addressing, torch's SGD update
-// restated per element, lerp_elems, the error plumbing and host-side launch helpers. The kernels
+// restated per element, lerp_elems, the error plumbing, the host-side launch helpers and the
+// runtime-code -> compile-time-tag dispatch (with_pair, with_dtype, with_io, ...). The kernels
 // live in edt_outer.hip (DiLoCo), edt_merge.hip (pair merge, lerp), edt_slerp.hip (SLERP) and
 // their C ABI (include/edt_sync.h) beside them; edt_abi.hip holds the error message and version.
 //
@@ -453,5 +454,59 @@ inline bool valid_pair(int gdt, int wdt) {
 
 
 inline bool is_pow2(int k) { return k > 0 && (k & (k - 1)) == 0; }
+
+inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
+template <int V> using Int = std::integral_constant<int, V>;
+template <bool V> using Bool = std::integral_constant<bool, V>;
+
+// host dispatch: a runtime code picks the compile-time tag the generic lambda f is called with
+// (the entries have validated the codes), so a launch site is one nested call
+
+template <class F>
+int with_pair(int gdt, int wdt, F&& f) {            // (master, worker) dtype: valid_pair's three
+    if (gdt == EDT_F32 && wdt == EDT_F32) return f(Int<EDT_F32>{}, Int<EDT_F32>{});
+    if (gdt == EDT_F32) return f(Int<EDT_F32>{}, Int<EDT_BF16>{});
+    return f(Int<EDT_BF16>{}, Int<EDT_BF16>{});
+}
+
+template <class F>
+int with_dtype(int gdt, F&& f) {
+    return gdt == EDT_F32 ? f(Int<EDT_F32>{}) : f(Int<EDT_BF16>{});
+}
+
+template <class F>
+int with_io(int in_dt, int out_dt, F&& f) {        // (input, output) dtype of the merges: all four
+    return with_dtype(in_dt, [&](auto I) { return with_dtype(out_dt, [&](auto O) { return f(I, O); }); });
+}
+
+template <class F>
+int with_fmt(int fmt, F&& f) {
+    return fmt == EDT_MXFP8 ? f(Int<EDT_MXFP8>{}) : f(Int<EDT_MXFP4>{});
+}
+
+template <class F>
+int with_bool(bool b, F&& f) {
+    return b ? f(Bool<true>{}) : f(Bool<false>{});
+}
+
+// (KC, DIV): compile-time worker counts for the common populations of a table, else the generic
+// loop (KC = 0, also what K = 0 asks for); the divisor is K_total. KC_FUSED (the fused and list
+// kernels): 1, 2, 4, 8 with the multiply, 3 with the division; KC_QUANT (the quantized partial): 8.
+enum { KC_QUANT = 0, KC_FUSED = 1 };
+template <int TABLE, class F>
+int with_kc_div(int K, bool div_exact, F&& f) {
+    if constexpr (TABLE == KC_FUSED) {
+        if (K == 1 && !div_exact) return f(Int<1>{}, Int<0>{});
+        if (K == 2 && !div_exact) return f(Int<2>{}, Int<0>{});
+        if (K == 3 && div_exact) return f(Int<3>{}, Int<1>{});
+        if (K == 4 && !div_exact) return f(Int<4>{}, Int<0>{});
+    }
+    if (K == 8 && !div_exact) return f(Int<8>{}, Int<0>{});
+    return div_exact ? f(Int<0>{}, Int<1>{}) : f(Int<0>{}, Int<0>{});
+}
 
 }  // namespace

@@ -209,17 +209,12 @@ int edt_pair_merge_tail(const void* b1, const void* b2, const void* m1, const vo
                      (!a.sgd.use_momentum || !has_momentum || aligned16(momentum_in));
     const unsigned g = grid_for(n, vec);
     hipStream_t s = (hipStream_t)stream;
-    if (gdt == EDT_F32 && wdt == EDT_F32) {
-        if (vec) pair_kernel<EDT_F32, EDT_F32, kVec><<<g, kBlock, 0, s>>>(a);
-        else pair_kernel<EDT_F32, EDT_F32, 1><<<g, kBlock, 0, s>>>(a);
-    } else if (gdt == EDT_F32) {
-        if (vec) pair_kernel<EDT_F32, EDT_BF16, kVec><<<g, kBlock, 0, s>>>(a);
-        else pair_kernel<EDT_F32, EDT_BF16, 1><<<g, kBlock, 0, s>>>(a);
-    } else {
-        if (vec) pair_kernel<EDT_BF16, EDT_BF16, kVec><<<g, kBlock, 0, s>>>(a);
-        else pair_kernel<EDT_BF16, EDT_BF16, 1><<<g, kBlock, 0, s>>>(a);
-    }
-    return check_launch("pair_kernel");
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_bool(vec, [&](auto V) {
+            pair_kernel<decltype(G)::value, decltype(W)::value, decltype(V)::value ? kVec : 1><<<g, kBlock, 0, s>>>(a);
+            return check_launch("pair_kernel");
+        });
+    });
 }
 
 int edt_pair_merge_population(const void* const* b1, const void* const* b2, const void* const* m1,
@@ -266,16 +261,12 @@ int edt_pair_merge_population(const void* const* b1, const void* const* b2, cons
     if (blocks > kGridBlockCap) return fail(EDT_ERR_ARG, "too many elements for one launch");
     const unsigned g = (unsigned)blocks;
     hipStream_t s = (hipStream_t)stream;
-#define EDT_POP(G, W)                                                                   \
-    do {                                                                                \
-        if (vec) pair_population_kernel<G, W, true><<<g, kBlock, 0, s>>>(P);            \
-        else pair_population_kernel<G, W, false><<<g, kBlock, 0, s>>>(P);              \
-    } while (0)
-    if (gdt == EDT_F32 && wdt == EDT_F32) EDT_POP(EDT_F32, EDT_F32);
-    else if (gdt == EDT_F32) EDT_POP(EDT_F32, EDT_BF16);
-    else EDT_POP(EDT_BF16, EDT_BF16);
-#undef EDT_POP
-    return check_launch("pair_population_kernel");
+    return with_pair(gdt, wdt, [&](auto G, auto W) {
+        return with_bool(vec, [&](auto V) {
+            pair_population_kernel<decltype(G)::value, decltype(W)::value, decltype(V)::value><<<g, kBlock, 0, s>>>(P);
+            return check_launch("pair_population_kernel");
+        });
+    });
 }
 
 int edt_lerp(const void* v0, const void* v1, int in_dt, void* out, int out_dt, int cdt, uint64_t n,
@@ -289,23 +280,20 @@ int edt_lerp(const void* v0, const void* v1, int in_dt, void* out, int out_dt, i
     const bool vec = aligned16(v0) && aligned16(v1) && aligned16(out);
     const unsigned g = grid_for(n, vec);
     hipStream_t s = (hipStream_t)stream;
-#define EDT_LERP(I, O, C)                                                                  \
-    do {                                                                                   \
-        if (vec) lerp_kernel<I, O, C, kVec><<<g, kBlock, 0, s>>>(v0, v1, out, n, c0, c1);   \
-        else lerp_kernel<I, O, C, 1><<<g, kBlock, 0, s>>>(v0, v1, out, n, c0, c1);          \
-    } while (0)
-    if (in_dt == EDT_F32) {
-        if (out_dt == EDT_F32) EDT_LERP(EDT_F32, EDT_F32, EDT_F32);
-        else EDT_LERP(EDT_F32, EDT_BF16, EDT_F32);
-    } else if (cdt == EDT_F32) {
-        if (out_dt == EDT_F32) EDT_LERP(EDT_BF16, EDT_F32, EDT_F32);
-        else EDT_LERP(EDT_BF16, EDT_BF16, EDT_F32);
-    } else {
-        if (out_dt == EDT_F32) EDT_LERP(EDT_BF16, EDT_F32, EDT_BF16);
-        else EDT_LERP(EDT_BF16, EDT_BF16, EDT_BF16);
-    }
-#undef EDT_LERP
-    return check_launch("lerp_kernel");
+    return with_io(in_dt, out_dt, [&](auto I, auto O) {
+        return with_dtype(cdt, [&](auto C) {
+            return with_bool(vec, [&](auto V) {
+                constexpr int IDT = decltype(I)::value, CDT = decltype(C)::value;
+                if constexpr (IDT == EDT_F32 && CDT == EDT_BF16) {       // refused above: no such kernel
+                    return fail(EDT_ERR_ARG, "bf16 compute of fp32 inputs unsupported");
+                } else {
+                    lerp_kernel<IDT, decltype(O)::value, CDT, decltype(V)::value ? kVec : 1>
+                        <<<g, kBlock, 0, s>>>(v0, v1, out, n, c0, c1);
+                    return check_launch("lerp_kernel");
+                }
+            });
+        });
+    });
 }
 
 

@@ -291,16 +291,15 @@ int pair_sums(const void* v0, const void* v1, int in_dt, void* out, int out_dt, 
     const uint64_t units = (uint64_t)nchunks * upc;
     for (uint64_t u0 = 0; u0 < units; u0 += kUnitGridCap) {       // > 16.7M units: several launches
         const unsigned g = unit_grid(units - u0);
-#define EDT_PS(I, E, O) pair_sums_kernel<I, E, O><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, rows, t, seg_ptrs, u0, zero_word)
-        if (!emit) {
-            if (in_dt == EDT_F32) EDT_PS(EDT_F32, false, EDT_F32);
-            else EDT_PS(EDT_BF16, false, EDT_F32);
-        } else if (in_dt == EDT_F32 && out_dt == EDT_F32) EDT_PS(EDT_F32, true, EDT_F32);
-        else if (in_dt == EDT_F32) EDT_PS(EDT_F32, true, EDT_BF16);
-        else if (out_dt == EDT_F32) EDT_PS(EDT_BF16, true, EDT_F32);
-        else EDT_PS(EDT_BF16, true, EDT_BF16);
-#undef EDT_PS
-        int rc = check_launch(emit ? "pair_sums_kernel (speculative)" : "pair_sums_kernel");
+        int rc = with_dtype(in_dt, [&](auto I) {
+            auto launch = [&](auto E, auto O) {
+                pair_sums_kernel<decltype(I)::value, decltype(E)::value, decltype(O)::value>
+                    <<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, rows, t, seg_ptrs, u0, zero_word);
+                return check_launch(emit ? "pair_sums_kernel (speculative)" : "pair_sums_kernel");
+            };
+            if (!emit) return launch(Bool<false>{}, Int<EDT_F32>{});     // no output: one ODT
+            return with_dtype(out_dt, [&](auto O) { return launch(Bool<true>{}, O); });
+        });
         if (rc) return rc;
     }
     // rows per chunk: 128 (level 0, one per unit's wave), 32 (level 2, one per unit) or 128 / kStatsTPW
@@ -889,6 +888,21 @@ __global__ __launch_bounds__(kBlock, EDT_NEED_MIN_WAVES) void slerp_need_kernel(
         rows[unit_slot(u, units) * NT + lane] = (ts2[0][lane] + ts2[1][lane]) + (ts2[2][lane] + ts2[3][lane]);
 }
 
+// the member count of a pass (1 .. kGramMaxMembers, checked by the callers) as a tag
+template <class F>
+int with_members(int D, F&& f) {
+    switch (D) {
+        case 1: return f(Int<1>{});
+        case 2: return f(Int<2>{});
+        case 3: return f(Int<3>{});
+        case 4: return f(Int<4>{});
+        case 5: return f(Int<5>{});
+        case 6: return f(Int<6>{});
+        case 7: return f(Int<7>{});
+        default: return f(Int<8>{});
+    }
+}
+
 // host: one needed-sums pass over the D members of `mem` (their order is the layout's) into sums
 // ([nchunks][need_nt(D)]; `rows`: the level-4 row scratch, nchunks x 8 x need_nt(D) doubles);
 // emit: also every child's lerp-branch output (S.out, S.t, S.zero_word).
@@ -904,30 +918,19 @@ inline int need_sums(const Members& mem, int D, const NeedSpec& S, int in_dt, in
     const uint64_t units = (uint64_t)nchunks * upc;
     for (uint64_t u0 = 0; u0 < units; u0 += kUnitGridCap) {
         const unsigned g = unit_grid(units - u0);
-#define EDT_NK(M)                                                                                          \
-    case M:                                                                                                \
-        if (tri) {                                                                                         \
-            if (in_dt == EDT_F32) slerp_need_kernel<EDT_F32, M, false, EDT_BF16, true><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0); \
-            else slerp_need_kernel<EDT_BF16, M, false, EDT_BF16, true><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0); \
-        } else if (!emit) {                                                                                \
-            if (in_dt == EDT_F32) slerp_need_kernel<EDT_F32, M><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0); \
-            else slerp_need_kernel<EDT_BF16, M><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0);    \
-        } else if (in_dt == EDT_F32 && out_dt == EDT_F32) {                                                \
-            slerp_need_kernel<EDT_F32, M, true, EDT_F32><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0); \
-        } else if (in_dt == EDT_F32) {                                                                     \
-            slerp_need_kernel<EDT_F32, M, true, EDT_BF16><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0); \
-        } else if (out_dt == EDT_F32) {                                                                    \
-            slerp_need_kernel<EDT_BF16, M, true, EDT_F32><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0); \
-        } else {                                                                                           \
-            slerp_need_kernel<EDT_BF16, M, true, EDT_BF16><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0); \
-        }                                                                                                  \
-        break;
-        switch (D) {
-            EDT_NK(1) EDT_NK(2) EDT_NK(3) EDT_NK(4) EDT_NK(5) EDT_NK(6) EDT_NK(7) EDT_NK(8)
-            default: break;
-        }
-#undef EDT_NK
-        int rc = check_launch(emit ? "slerp_need_kernel (speculative)" : "slerp_need_kernel");
+        // the stats passes (triangle or needed) have no output: one ODT (EDT_BF16, the kernel's default)
+        int rc = with_members(D, [&](auto M) {
+            return with_dtype(in_dt, [&](auto I) {
+                auto launch = [&](auto E, auto O, auto T) {
+                    slerp_need_kernel<decltype(I)::value, decltype(M)::value, decltype(E)::value, decltype(O)::value,
+                                      decltype(T)::value><<<g, kBlock, 0, s>>>(mem, S, chunk_desc, nchunks, rows, u0);
+                    return check_launch(emit ? "slerp_need_kernel (speculative)" : "slerp_need_kernel");
+                };
+                if (tri) return launch(Bool<false>{}, Int<EDT_BF16>{}, Bool<true>{});
+                if (!emit) return launch(Bool<false>{}, Int<EDT_BF16>{}, Bool<false>{});
+                return with_dtype(out_dt, [&](auto O) { return launch(Bool<true>{}, O, Bool<false>{}); });
+            });
+        });
         if (rc) return rc;
     }
     return launch_tree_reduce(rows, tri ? D * (D + 1) / 2 : need_nt(D), kGramRows, upc, 1, nchunks, sums, s);
@@ -1280,23 +1283,14 @@ __global__ __launch_bounds__(kBlock) void slerp_blend_mm_kernel(Members mem, Pop
 inline int launch_blend_mm(const Members& mem, int D, const PopBlend& pb, int in_dt, int out_dt,
                            const uint64_t* chunk_desc, int64_t nchunks, hipStream_t s) {
     const unsigned g = slerp_spec_grid(nchunks);
-#define EDT_BMM(M)                                                                                            \
-    case M:                                                                                                   \
-        if (in_dt == EDT_F32 && out_dt == EDT_F32)                                                            \
-            slerp_blend_mm_kernel<EDT_F32, EDT_F32, M><<<g, kBlock, 0, s>>>(mem, pb, chunk_desc, nchunks);   \
-        else if (in_dt == EDT_F32)                                                                            \
-            slerp_blend_mm_kernel<EDT_F32, EDT_BF16, M><<<g, kBlock, 0, s>>>(mem, pb, chunk_desc, nchunks);  \
-        else if (out_dt == EDT_F32)                                                                           \
-            slerp_blend_mm_kernel<EDT_BF16, EDT_F32, M><<<g, kBlock, 0, s>>>(mem, pb, chunk_desc, nchunks);  \
-        else                                                                                                  \
-            slerp_blend_mm_kernel<EDT_BF16, EDT_BF16, M><<<g, kBlock, 0, s>>>(mem, pb, chunk_desc, nchunks); \
-        break;
-    switch (D) {
-        EDT_BMM(1) EDT_BMM(2) EDT_BMM(3) EDT_BMM(4) EDT_BMM(5) EDT_BMM(6) EDT_BMM(7) EDT_BMM(8)
-        default: return fail(EDT_ERR_ARG, "member-major blend over %d parents", D);
-    }
-#undef EDT_BMM
-    return check_launch("slerp_blend_mm_kernel");
+    if (D < 1 || D > kGramMaxMembers) return fail(EDT_ERR_ARG, "member-major blend over %d parents", D);
+    return with_members(D, [&](auto M) {
+        return with_io(in_dt, out_dt, [&](auto I, auto O) {
+            slerp_blend_mm_kernel<decltype(I)::value, decltype(O)::value, decltype(M)::value>
+                <<<g, kBlock, 0, s>>>(mem, pb, chunk_desc, nchunks);
+            return check_launch("slerp_blend_mm_kernel");
+        });
+    });
 }
 
 int slerp_stats_impl(const void* v0, const void* v1, int in_dt, const uint64_t* chunk_desc, int64_t nchunks,
@@ -1318,15 +1312,17 @@ int slerp_blend_impl(const void* v0, const void* v1, int in_dt, void* out, int o
     const uint64_t units = (uint64_t)nchunks * (kTileSlots / kWavesPerBlock);
     for (uint64_t u0 = 0; u0 < units; u0 += kUnitGridCap) {
         const unsigned g = unit_grid(units - u0);
-#define EDT_BT(I, O, N) slerp_blend_tile_kernel<I, O, N><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, seg_ptrs, u0)
-        if (in_dt == EDT_F32 && out_dt == EDT_F32) EDT_BT(EDT_F32, EDT_F32, false);
-        else if (in_dt == EDT_F32) EDT_BT(EDT_F32, EDT_BF16, false);
-        else if (out_dt == EDT_F32 && nt) EDT_BT(EDT_BF16, EDT_F32, kNt);
-        else if (out_dt == EDT_F32) EDT_BT(EDT_BF16, EDT_F32, false);
-        else if (nt) EDT_BT(EDT_BF16, EDT_BF16, kNt);
-        else EDT_BT(EDT_BF16, EDT_BF16, false);
-#undef EDT_BT
-        int rc = check_launch("slerp_blend_tile_kernel");
+        int rc = with_io(in_dt, out_dt, [&](auto I, auto O) {
+            auto launch = [&](auto N) {
+                slerp_blend_tile_kernel<decltype(I)::value, decltype(O)::value, decltype(N)::value>
+                    <<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, seg_ptrs, u0);
+                return check_launch("slerp_blend_tile_kernel");
+            };
+            if constexpr (decltype(I)::value == EDT_BF16) {      // non-temporal loads: bf16 parents only
+                if (nt) return launch(Bool<kNt>{});
+            }
+            return launch(Bool<false>{});
+        });
         if (rc) return rc;
     }
     return EDT_OK;
@@ -1657,6 +1653,264 @@ __global__ __launch_bounds__(kBlock) void refdot_coef_kernel(const float* ref_do
     if (dot_out) dot_out[s] = dot;
 }
 
+// ---------------------------------------------------------------------------------------
+// host: what the population entries share
+
+// the redo blends / any table blend with a redo mask: grid-stride over chunks (most are skipped)
+int blend_redo(const void* v0, const void* v1, int in_dt, void* out, int out_dt, const uint64_t* chunk_desc,
+               int64_t nchunks, const float* coef, const uint64_t* seg_ptrs, const int32_t* redo,
+               const int32_t* any, hipStream_t s) {
+    const unsigned g = slerp_spec_grid(nchunks);
+    return with_io(in_dt, out_dt, [&](auto I, auto O) {
+        constexpr int IDT = decltype(I)::value;
+        constexpr bool NT = EDT_NT_SLERP != 0 && IDT == EDT_BF16;     // fp32 parents: default loads
+        slerp_blend_kernel<IDT, decltype(O)::value, NT>
+            <<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, seg_ptrs, redo, any);
+        return check_launch("slerp_blend_kernel");
+    });
+}
+
+// The any-redo word of a speculative workspace: its last double (zeroed by the first pass, set by
+// a coefficient kernel that sends a segment to the SLERP branch; clear, the redo grid exits at
+// once). One address per workspace kind: the pair form's (edt_slerp_sums_doubles(3, .)) and the
+// population form's (edt_slerp_population_speculative_doubles).
+inline int32_t* any_redo_word(double* workspace, uint64_t doubles) {
+    return reinterpret_cast<int32_t*>(workspace + doubles - 1);
+}
+inline int32_t* pair_any_redo(double* partial, int64_t nchunks) {
+    return any_redo_word(partial, edt_slerp_sums_doubles(3, nchunks));
+}
+inline int32_t* population_any_redo(double* partial, int npairs, int64_t nchunks) {
+    return any_redo_word(partial, edt_slerp_population_speculative_doubles(npairs, nchunks));
+}
+
+// child q's slices of the per-child arrays: coef [npairs][nseg][2], dot_out and redo [npairs][nseg]
+// (either may be absent)
+template <class C>
+struct ChildSlices {
+    C* coef;
+    float* dot;
+    int32_t* redo;
+};
+template <class C>
+inline ChildSlices<C> child_slices(int q, int nseg, C* coef, float* dot_out = nullptr, int32_t* redo = nullptr) {
+    const size_t at = (size_t)nseg * q;
+    return {coef + 2 * at, dot_out ? dot_out + at : nullptr, redo ? redo + at : nullptr};
+}
+
+// children [q0, q0 + <= 16) as one co-located launch group (redo: null for the two-pass blends)
+inline BlendChildren colocated_group(const void* const* members, const int32_t* pairs, int npairs, void* const* outs,
+                                     int q0, int nseg, float* coef, int32_t* redo) {
+    BlendChildren B;
+    memset(&B, 0, sizeof(B));
+    B.nchildren = npairs - q0 < kBlendMaxChildren ? npairs - q0 : kBlendMaxChildren;
+    for (int k = 0; k < B.nchildren; ++k) {
+        const int q = q0 + k;
+        const auto c = child_slices(q, nseg, coef, nullptr, redo);
+        B.v0[k] = members[pairs[2 * q]];
+        B.v1[k] = members[pairs[2 * q + 1]];
+        B.out[k] = outs[q];
+        B.coef[k] = c.coef;
+        B.redo[k] = c.redo;
+    }
+    return B;
+}
+
+// The argument checks of the entries that take (members, pairs, outs), in the one order all three
+// report them: dtypes, counts, nothing to do, null tables, each member, then per child its pair,
+// its output and the output against every member. What the entries mean to differ in is said here.
+// (All three have outputs: the entries without, edt_slerp_needed_*, check their members in the
+// plan's first-use order after planning, so "no outputs" is not a case of this function.)
+struct PopCheck {
+    // kGramMaxMembers (the member-major kernels hold that many parents), or 0: any number (the
+    // speculative entry: more than 8 distinct parents take its co-located pass)
+    int max_members;
+    // kBlendMaxChildren (edt_slerp_blend_children is one member-major launch), or 0: any number
+    int max_children;
+    // true: an output must be clear of every member's n elements byte-wise ("overlaps": the
+    // speculative pass writes the outputs before the redo pass reads the parents); false: it only
+    // must be another pointer ("aliases")
+    bool overlap;
+    uint64_t n;
+};
+constexpr PopCheck kCheckTwoPass = {kGramMaxMembers, 0, false, 0};
+constexpr PopCheck kCheckBlendChildren = {kGramMaxMembers, kBlendMaxChildren, false, 0};
+inline PopCheck check_speculative(uint64_t n) { return {0, 0, true, n}; }
+
+// other_negative / other_empty / other_null: the entry's own counts and buffers (segments, chunks,
+// workspaces) folded into the same three refusals. todo = false: a valid call with nothing to do.
+int check_population(const PopCheck& c, const void* const* members, int nmembers, int in_dt, const int32_t* pairs,
+                     int npairs, void* const* outs, int out_dt, bool other_negative, bool other_empty,
+                     bool other_null, bool& todo) {
+    todo = false;
+    if ((in_dt | out_dt) & ~1) return fail(EDT_ERR_ARG, "unsupported dtype");
+    if (c.max_members && (nmembers < 1 || nmembers > c.max_members))
+        return fail(EDT_ERR_ARG, "member count %d out of range [1, %d]", nmembers, c.max_members);
+    if (c.max_children && (npairs < 0 || npairs > c.max_children))
+        return fail(EDT_ERR_ARG, "child count %d out of range [0, %d]", npairs, c.max_children);
+    if (nmembers < 1 || npairs < 0 || other_negative)
+        return fail(EDT_ERR_ARG, c.max_members ? "negative count" : "bad count");
+    if (npairs == 0 || other_empty) return EDT_OK;
+    if (!members || !pairs || !outs || other_null) return fail(EDT_ERR_ARG, "null buffer");
+    for (int m = 0; m < nmembers; ++m)
+        if (!members[m] || !aligned16(members[m])) return fail(EDT_ERR_ARG, "member %d is null or not 16-byte aligned", m);
+    const uint64_t in_bytes = c.n * (in_dt == EDT_BF16 ? 2 : 4), out_bytes = c.n * (out_dt == EDT_BF16 ? 2 : 4);
+    for (int q = 0; q < npairs; ++q) {
+        const int i = pairs[2 * q], j = pairs[2 * q + 1];
+        if (i < 0 || j < 0 || i >= nmembers || j >= nmembers) return fail(EDT_ERR_ARG, "pair %d: member out of range", q);
+        if (!outs[q] || !aligned16(outs[q])) return fail(EDT_ERR_ARG, "output %d is null or not 16-byte aligned", q);
+        for (int m = 0; m < nmembers; ++m) {
+            if (c.overlap ? bytes_overlap(outs[q], out_bytes, members[m], in_bytes) : outs[q] == members[m])
+                return fail(EDT_ERR_ARG, c.overlap ? "output %d overlaps member %d" : "output %d aliases member %d", q, m);
+        }
+    }
+    todo = true;
+    return EDT_OK;
+}
+
+// The population plan: everything the population entries derive from (pairs, nmembers) — the
+// distinct parents in first-use order (compact ids), the children's compact parents, the GramPlan
+// of the pair graph and, when asked (PlanFor), where each child lands in its component's emit table
+// and the verdict on the speculative form. edt_slerp_population, edt_slerp_population_speculative,
+// the edt_slerp_needed_* entries and edt_slerp_population_layout all read this one object: a table
+// row equals the population pass's sums, and the form the layout reports is the form launched.
+enum PopForm { kFormMemberMajor, kFormColocated };
+
+struct PopPlan {
+    int D = 0;                                 // distinct parents
+    std::vector<int> orig;                     // compact -> member index
+    std::vector<int> A, B;                     // children's compact parents
+    bool planned = false;                      // G holds the pair graph's plan (D <= kGramMaxMembers)
+    GramPlan G;                                // (else only the co-located speculative form runs)
+    // kPlanLaunch / kPlanReport (planned): G.need[k] holds each component's emit table but for the output pointers,
+    // which bind_outputs() fills from the entry's outs; slot / dup say where child q went
+    std::vector<int> slot;                     // c: ring edge c forward, 8 + c: reversed, 16 + e: picked pair e
+    std::vector<char> dup;                     // a further child of a pair already emitted (NeedSpec::xslot)
+    int npair[kGramMaxMembers] = {};           // per component: distinct ordered pairs,
+    int npicked[kGramMaxMembers] = {};         // those off the ring (chords, self-pairs; every pair of a triangle),
+    int ndots[kGramMaxMembers] = {};           // distinct unordered dots
+    PopForm form = kFormColocated;             // the speculative form, and what decided it
+    const char* why = "";
+
+    void bind_outputs(void* const* outs) {     // form == kFormMemberMajor
+        for (size_t q = 0; q < slot.size(); ++q) {
+            NeedSpec& S = G.need[G.comp_of[A[q]]];
+            const int c = slot[q];
+            if (dup[q]) continue;
+            (c < 8 ? S.out_fwd[c] : c < 16 ? S.out_rev[c - 8] : S.out[c - 16]) = outs[q];
+        }
+        int nx[kGramMaxMembers] = {};
+        for (size_t q = 0; q < slot.size(); ++q)
+            if (dup[q]) { const int k = G.comp_of[A[q]]; G.need[k].xout[nx[k]++] = outs[q]; }
+    }
+};
+
+// What the caller wants of the plan: the sums' layout only; that and the emit tables to launch the
+// speculative form from; or the same to report (every count, whatever the form turns out to be).
+enum PlanFor { kPlanSums, kPlanLaunch, kPlanReport };
+
+// pairs: npairs >= 0 children (non-null when npairs > 0), nmembers >= 1, nchunks >= 0 (the callers'
+// checks); refuses a pair naming a member outside [0, nmembers).
+int population_plan(const int32_t* pairs, int npairs, int nmembers, int64_t nchunks, PlanFor want, PopPlan& P) {
+    const bool many = npairs > kBlendMaxChildren;
+    if (many) P.why = "more children than one member-major launch holds";
+    // a launch of that many children is co-located whatever their graph: it needs nothing else of
+    // the plan (plan_gram tries up to 5,040 cyclic orders); the report still lists the components
+    if (want == kPlanLaunch && many) return EDT_OK;
+    std::vector<int> compact(nmembers, -1);
+    P.A.assign(npairs, 0);
+    P.B.assign(npairs, 0);
+    for (int q = 0; q < npairs; ++q)
+        for (int e = 0; e < 2; ++e) {
+            const int m = pairs[2 * q + e];
+            if (m < 0 || m >= nmembers) return fail(EDT_ERR_ARG, "pair %d: member out of range", q);
+            if (compact[m] < 0) {
+                compact[m] = P.D++;
+                P.orig.push_back(m);
+            }
+            (e ? P.B : P.A)[q] = compact[m];
+        }
+    if (P.D > kGramMaxMembers) {
+        P.why = "more distinct parents than the member-major kernels hold";
+        return EDT_OK;
+    }
+    GramPlan& G = P.G;
+    plan_gram(P.D, P.A.data(), P.B.data(), npairs, nchunks, G);
+    P.planned = true;
+    if (want == kPlanSums) return EDT_OK;
+    // each child onto its component's emit table: the first child of an ordered pair takes the
+    // pair's slot (a ring slot, or the next picked pair), the others are duplicates stored from the
+    // same registers. The tables are filled while the form still fits; the counts run on.
+    bool fits = !many;
+    for (int k = 0; k < G.ncomp && fits; ++k)
+        if (G.kind[k] != kNeed) { fits = false; P.why = "a component on the triangle layout"; }
+    int seen[kGramMaxMembers][kGramMaxMembers];               // ordered pair -> its slot
+    memset(seen, -1, sizeof(seen));
+    P.slot.assign(npairs, 0);
+    P.dup.assign(npairs, 0);
+    for (int q = 0; q < npairs; ++q) {
+        const int a = P.A[q], b = P.B[q], k = G.comp_of[a], n = G.size[k];
+        const int pa = G.pos[a], pb = G.pos[b];
+        NeedSpec& S = G.need[k];
+        int& s = seen[a][b];
+        if (s >= 0) {                                       // a duplicate: same registers
+            P.dup[q] = 1;
+            P.slot[q] = s;
+            if (!fits) continue;
+            if (S.nextra == kNeedMaxOut) { fits = false; P.why = "more duplicate children than a component stores"; continue; }
+            S.xslot[S.nextra++] = s;
+            continue;
+        }
+        ++P.npair[k];
+        P.ndots[k] += a != b && seen[b][a] < 0;
+        if (G.kind[k] == kNeed && pa != pb && GramPlan::ring_edge(pa, pb, n) >= 0) {
+            const bool forward = pb == (pa + 1) % n && (n >= 3 || pa == 0);
+            s = forward ? pa : 8 + pb;
+            if (fits) (forward ? S.fwd : S.rev) |= 1u << (s & 7);
+        } else {                                            // a chord or a self-pair: a picked pair
+            s = 16 + P.npicked[k]++;
+            if (!fits) continue;
+            if (S.nemit == kNeedChordEmits) { fits = false; P.why = "more picked pairs than a component emits"; continue; }
+            S.ea[S.nemit] = pa;
+            S.eb[S.nemit++] = pb;
+        }
+        P.slot[q] = s;
+    }
+    if (fits) P.form = kFormMemberMajor;
+    return EDT_OK;
+}
+
+// the needed-sums entries' plan: their argument checks, then the population's plan (no emit)
+int needed_plan(const int32_t* pairs, int npairs, int nmembers, int64_t nchunks, PopPlan& P) {
+    if (nmembers < 1 || nmembers > kGramMaxMembers)
+        return fail(EDT_ERR_ARG, "member count %d out of range [1, %d]", nmembers, kGramMaxMembers);
+    if (npairs < 1 || !pairs) return fail(EDT_ERR_ARG, "no pairs");
+    if (nchunks < 0) return fail(EDT_ERR_ARG, "negative chunk count");
+    return population_plan(pairs, npairs, nmembers, nchunks, kPlanSums, P);
+}
+
+// the plan's distinct parents as the kernels take them
+inline Members plan_members(const PopPlan& P, const void* const* members) {
+    Members mem;
+    memset(&mem, 0, sizeof(mem));
+    for (int d = 0; d < P.D; ++d) mem.p[d] = members[P.orig[d]];
+    return mem;
+}
+
+// child q's coefficients from its component's sums (gram: the table / workspace the sums are in);
+// redo and any: the speculative form's
+int plan_child_coef(const PopPlan& P, int q, const double* gram, const int32_t* seg_first_chunk, int nseg,
+                    const double* t, double dot_threshold, double eps, float* coef, float* dot_out, int32_t* redo,
+                    int32_t* any, hipStream_t s) {
+    const GramPlan& G = P.G;
+    const int i = P.A[q], j = P.B[q], k = G.comp_of[i];           // i and j share a component
+    const auto c = child_slices(q, nseg, coef, dot_out, redo);
+    slerp_gram_coef_kernel<<<coef_grid(nseg), kBlock, 0, s>>>(gram + G.off[k], G.nt(k), G.norm_index(i), G.norm_index(j),
+                                                              G.dot_index(i, j), seg_first_chunk, nseg, t,
+                                                              (float)dot_threshold, (float)eps, c.coef, c.dot, c.redo, any);
+    return check_launch("slerp_gram_coef_kernel");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1765,65 +2019,29 @@ int edt_slerp_population(const void* const* members, int nmembers, int in_dt, co
                          const int32_t* seg_first_chunk, int nseg, const double* t, double dot_threshold,
                          double eps, double* gram, float* coef, float* dot_out, void* stream) {
     g_err[0] = 0;
-    if ((in_dt | out_dt) & ~1) return fail(EDT_ERR_ARG, "unsupported dtype");
-    if (nmembers < 1 || nmembers > kGramMaxMembers)
-        return fail(EDT_ERR_ARG, "member count %d out of range [1, %d]", nmembers, kGramMaxMembers);
-    if (npairs < 0 || nseg < 0 || nchunks < 0) return fail(EDT_ERR_ARG, "negative count");
-    if (npairs == 0 || nseg == 0 || nchunks == 0) return EDT_OK;
-    if (!members || !pairs || !outs || !chunk_desc || !seg_first_chunk || !t || !gram || !coef)
-        return fail(EDT_ERR_ARG, "null buffer");
-    Members mem;
-    memset(&mem, 0, sizeof(mem));
-    for (int m = 0; m < nmembers; ++m) {
-        if (!aligned16(members[m]) || !members[m]) return fail(EDT_ERR_ARG, "member %d is null or not 16-byte aligned", m);
-        mem.p[m] = members[m];
-    }
-    for (int q = 0; q < npairs; ++q) {
-        const int i = pairs[2 * q], j = pairs[2 * q + 1];
-        if (i < 0 || j < 0 || i >= nmembers || j >= nmembers) return fail(EDT_ERR_ARG, "pair %d: member out of range", q);
-        if (!outs[q] || !aligned16(outs[q])) return fail(EDT_ERR_ARG, "output %d is null or not 16-byte aligned", q);
-        for (int m = 0; m < nmembers; ++m)
-            if (outs[q] == members[m]) return fail(EDT_ERR_ARG, "output %d aliases member %d", q, m);
-    }
+    bool todo;
+    int rc = check_population(kCheckTwoPass, members, nmembers, in_dt, pairs, npairs, outs, out_dt,
+                              nseg < 0 || nchunks < 0, nseg == 0 || nchunks == 0,
+                              !chunk_desc || !seg_first_chunk || !t || !gram || !coef, todo);
+    if (rc || !todo) return rc;
     hipStream_t s = (hipStream_t)stream;
     // the Gram pass and the blends run over the distinct parents only (compact indices)
-    int compact[kGramMaxMembers];
-    int D = 0;
-    for (int m = 0; m < nmembers; ++m) compact[m] = -1;
-    memset(&mem, 0, sizeof(mem));
-    for (int q = 0; q < npairs; ++q)
-        for (int e = 0; e < 2; ++e) {
-            const int m = pairs[2 * q + e];
-            if (compact[m] < 0) {
-                compact[m] = D;
-                mem.p[D++] = members[m];
-            }
-        }
+    PopPlan P;
+    rc = population_plan(pairs, npairs, nmembers, nchunks, kPlanSums, P);
+    if (rc) return rc;
+    const Members mem = plan_members(P, members);
     // the sums per component of the pair graph (GramPlan): the needed layout where it applies
     // (r5); the chunk rows of every component first, one shared level-4 row scratch after them
     // (each component's pass has finished with it before the next one starts: one stream)
-    GramPlan G;
-    int rc = EDT_OK;
-    {
-        std::vector<int> A(npairs), B(npairs);
-        for (int q = 0; q < npairs; ++q) { A[q] = compact[pairs[2 * q]]; B[q] = compact[pairs[2 * q + 1]]; }
-        plan_gram(D, A.data(), B.data(), npairs, nchunks, G);
-    }
+    const GramPlan& G = P.G;
     uint64_t scratch = 0;
     for (int k = 0; k < G.ncomp; ++k) scratch += (uint64_t)nchunks * G.nt(k);
     for (int k = 0; k < G.ncomp; ++k) {
         rc = plan_component_sums(G, k, mem.p, in_dt, chunk_desc, nchunks, gram, gram + scratch, s);
         if (rc) return rc;
     }
-    const unsigned gc = coef_grid(nseg);
     for (int q = 0; q < npairs; ++q) {
-        const int i = compact[pairs[2 * q]], j = compact[pairs[2 * q + 1]];
-        const int k = G.comp_of[i];                   // i and j share a component
-        slerp_gram_coef_kernel<<<gc, kBlock, 0, s>>>(gram + G.off[k], G.nt(k), G.norm_index(i), G.norm_index(j),
-                                                     G.dot_index(i, j), seg_first_chunk, nseg, t,
-                                                     (float)dot_threshold, (float)eps, coef + 2 * (size_t)nseg * q,
-                                                     dot_out ? dot_out + (size_t)nseg * q : nullptr);
-        rc = check_launch("slerp_gram_coef_kernel");
+        rc = plan_child_coef(P, q, gram, seg_first_chunk, nseg, t, dot_threshold, eps, coef, dot_out, nullptr, nullptr, s);
         if (rc) return rc;
     }
     // the blends: member-major when the children fit one launch, else co-located groups of <= 16
@@ -1833,32 +2051,20 @@ int edt_slerp_population(const void* const* members, int nmembers, int in_dt, co
         pb.n = npairs;
         for (int q = 0; q < npairs; ++q) {
             pb.out[q] = outs[q];
-            pb.coef[q] = coef + 2 * (size_t)nseg * q;
-            pb.a[q] = compact[pairs[2 * q]];
-            pb.b[q] = compact[pairs[2 * q + 1]];
+            pb.coef[q] = child_slices(q, nseg, coef).coef;
+            pb.a[q] = P.A[q];
+            pb.b[q] = P.B[q];
         }
-        return launch_blend_mm(mem, D, pb, in_dt, out_dt, chunk_desc, nchunks, s);
+        return launch_blend_mm(mem, P.D, pb, in_dt, out_dt, chunk_desc, nchunks, s);
     }
     for (int q0 = 0; q0 < npairs; q0 += kBlendMaxChildren) {
-        BlendChildren B;
-        memset(&B, 0, sizeof(B));
-        B.nchildren = npairs - q0 < kBlendMaxChildren ? npairs - q0 : kBlendMaxChildren;
-        for (int k = 0; k < B.nchildren; ++k) {
-            const int q = q0 + k;
-            B.v0[k] = members[pairs[2 * q]];
-            B.v1[k] = members[pairs[2 * q + 1]];
-            B.out[k] = outs[q];
-            B.coef[k] = coef + 2 * (size_t)nseg * q;
-        }
+        const BlendChildren B = colocated_group(members, pairs, npairs, outs, q0, nseg, coef, nullptr);
         rc = colocated_launches((uint64_t)nchunks, B.nchildren, [&](uint64_t c0, unsigned gb) {
-            if (in_dt == EDT_F32 && out_dt == EDT_F32)
-                slerp_blend_population_kernel<EDT_F32, EDT_F32><<<gb, kBlock, 0, s>>>(B, chunk_desc, nchunks, c0);
-            else if (in_dt == EDT_F32)
-                slerp_blend_population_kernel<EDT_F32, EDT_BF16><<<gb, kBlock, 0, s>>>(B, chunk_desc, nchunks, c0);
-            else if (out_dt == EDT_F32)
-                slerp_blend_population_kernel<EDT_BF16, EDT_F32><<<gb, kBlock, 0, s>>>(B, chunk_desc, nchunks, c0);
-            else
-                slerp_blend_population_kernel<EDT_BF16, EDT_BF16><<<gb, kBlock, 0, s>>>(B, chunk_desc, nchunks, c0);
+            with_io(in_dt, out_dt, [&](auto I, auto O) {
+                slerp_blend_population_kernel<decltype(I)::value, decltype(O)::value>
+                    <<<gb, kBlock, 0, s>>>(B, chunk_desc, nchunks, c0);
+                return 0;
+            });
         });
         if (rc) return rc;
     }
@@ -1874,33 +2080,21 @@ int edt_slerp_blend_children(const void* const* members, int nmembers, int in_dt
                              int npairs, void* const* outs, int out_dt, const uint64_t* chunk_desc,
                              int64_t nchunks, const float* coef, int nseg, void* stream) {
     g_err[0] = 0;
-    if ((in_dt | out_dt) & ~1) return fail(EDT_ERR_ARG, "unsupported dtype");
-    if (nmembers < 1 || nmembers > kGramMaxMembers)
-        return fail(EDT_ERR_ARG, "member count %d out of range [1, %d]", nmembers, kGramMaxMembers);
-    if (npairs < 0 || npairs > kBlendMaxChildren)
-        return fail(EDT_ERR_ARG, "child count %d out of range [0, %d]", npairs, kBlendMaxChildren);
-    if (nchunks < 0 || nseg < 0) return fail(EDT_ERR_ARG, "negative count");
-    if (npairs == 0 || nchunks == 0) return EDT_OK;
-    if (!members || !pairs || !outs || !chunk_desc || !coef) return fail(EDT_ERR_ARG, "null buffer");
-    Members mem;
+    bool todo;
+    int rc = check_population(kCheckBlendChildren, members, nmembers, in_dt, pairs, npairs, outs, out_dt,
+                              nchunks < 0 || nseg < 0, nchunks == 0, !chunk_desc || !coef, todo);
+    if (rc || !todo) return rc;
+    Members mem;                               // every member, at its own index: no plan
     memset(&mem, 0, sizeof(mem));
-    for (int m = 0; m < nmembers; ++m) {
-        if (!members[m] || !aligned16(members[m])) return fail(EDT_ERR_ARG, "member %d is null or not 16-byte aligned", m);
-        mem.p[m] = members[m];
-    }
     PopBlend pb;
     memset(&pb, 0, sizeof(pb));
     pb.n = npairs;
+    for (int m = 0; m < nmembers; ++m) mem.p[m] = members[m];
     for (int q = 0; q < npairs; ++q) {
-        const int i = pairs[2 * q], j = pairs[2 * q + 1];
-        if (i < 0 || j < 0 || i >= nmembers || j >= nmembers) return fail(EDT_ERR_ARG, "pair %d: member out of range", q);
-        if (!outs[q] || !aligned16(outs[q])) return fail(EDT_ERR_ARG, "output %d is null or not 16-byte aligned", q);
-        for (int m = 0; m < nmembers; ++m)
-            if (outs[q] == members[m]) return fail(EDT_ERR_ARG, "output %d aliases member %d", q, m);
         pb.out[q] = outs[q];
-        pb.coef[q] = coef + 2 * (size_t)nseg * q;
-        pb.a[q] = i;
-        pb.b[q] = j;
+        pb.coef[q] = child_slices(q, nseg, coef).coef;
+        pb.a[q] = pairs[2 * q];
+        pb.b[q] = pairs[2 * q + 1];
     }
     return launch_blend_mm(mem, nmembers, pb, in_dt, out_dt, chunk_desc, nchunks, (hipStream_t)stream);
 }
@@ -1918,34 +2112,19 @@ int edt_slerp_merge_speculative(const void* v0, const void* v1, int in_dt, void*
     if (!aligned16(v0) || !aligned16(v1) || !aligned16(out))
         return fail(EDT_ERR_ARG, "slerp buffers must be 16-byte aligned");
     // the first pass writes `out` while the second may still need both parents
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + n * (out_dt == EDT_BF16 ? 2 : 4);
-    const uint64_t isz = in_dt == EDT_BF16 ? 2 : 4;
-    for (const void* p : {v0, v1}) {
-        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), p1 = p0 + n * isz;
-        if (p0 < o1 && o0 < p1) return fail(EDT_ERR_ARG, "speculative SLERP needs an output apart from the parents");
-    }
+    const uint64_t in_bytes = n * (in_dt == EDT_BF16 ? 2 : 4), out_bytes = n * (out_dt == EDT_BF16 ? 2 : 4);
+    for (const void* p : {v0, v1})
+        if (bytes_overlap(p, in_bytes, out, out_bytes))
+            return fail(EDT_ERR_ARG, "speculative SLERP needs an output apart from the parents");
     hipStream_t s = (hipStream_t)stream;
-    // the any-redo flag: the last double of the workspace (edt_slerp_sums_doubles), zeroed by the
-    // first pass, set by the coefficient kernel when some segment takes the SLERP branch
-    int32_t* any = reinterpret_cast<int32_t*>(partial + edt_slerp_sums_doubles(3, nchunks) - 1);
+    int32_t* any = pair_any_redo(partial, nchunks);
     int rc = pair_sums(v0, v1, in_dt, out, out_dt, true, chunk_desc, nchunks, partial, t, nullptr, s, any);
     if (rc) return rc;
     slerp_coef_kernel<<<coef_grid(nseg), kBlock, 0, s>>>(partial, seg_first_chunk, nseg, t, (float)dot_threshold,
                                                          (float)eps, coef, dot_out, redo, any);
     rc = check_launch("slerp_coef_kernel");
     if (rc) return rc;
-    // the redo blends: grid-stride over chunks (most segments are skipped)
-    const unsigned g = slerp_spec_grid(nchunks);
-    constexpr bool kNtB = EDT_NT_SLERP != 0;
-    if (in_dt == EDT_F32 && out_dt == EDT_F32)
-        slerp_blend_kernel<EDT_F32, EDT_F32, false><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, nullptr, redo, any);
-    else if (in_dt == EDT_F32)
-        slerp_blend_kernel<EDT_F32, EDT_BF16, false><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, nullptr, redo, any);
-    else if (out_dt == EDT_F32)
-        slerp_blend_kernel<EDT_BF16, EDT_F32, kNtB><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, nullptr, redo, any);
-    else
-        slerp_blend_kernel<EDT_BF16, EDT_BF16, kNtB><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, nullptr, redo, any);
-    return check_launch("slerp_blend_kernel");
+    return blend_redo(v0, v1, in_dt, out, out_dt, chunk_desc, nchunks, coef, nullptr, redo, any, s);
 }
 
 int edt_slerp_population_speculative(const void* const* members, int nmembers, int in_dt, const int32_t* pairs,
@@ -1954,181 +2133,92 @@ int edt_slerp_population_speculative(const void* const* members, int nmembers, i
                                      double dot_threshold, double eps, double* partial, float* coef,
                                      float* dot_out, int32_t* redo, uint64_t n, void* stream) {
     g_err[0] = 0;
-    if ((in_dt | out_dt) & ~1) return fail(EDT_ERR_ARG, "unsupported dtype");
-    if (nmembers < 1 || npairs < 0 || nseg < 0 || nchunks < 0) return fail(EDT_ERR_ARG, "bad count");
-    if (npairs == 0 || nseg == 0 || nchunks == 0) return EDT_OK;
-    if (!members || !pairs || !outs || !chunk_desc || !seg_first_chunk || !t || !partial || !coef || !redo)
-        return fail(EDT_ERR_ARG, "null buffer");
-    const uint64_t isz = in_dt == EDT_BF16 ? 2 : 4, osz = out_dt == EDT_BF16 ? 2 : 4;
-    for (int m = 0; m < nmembers; ++m)
-        if (!members[m] || !aligned16(members[m])) return fail(EDT_ERR_ARG, "member %d is null or not 16-byte aligned", m);
-    for (int q = 0; q < npairs; ++q) {
-        const int i = pairs[2 * q], j = pairs[2 * q + 1];
-        if (i < 0 || j < 0 || i >= nmembers || j >= nmembers) return fail(EDT_ERR_ARG, "pair %d: member out of range", q);
-        if (!outs[q] || !aligned16(outs[q])) return fail(EDT_ERR_ARG, "output %d is null or not 16-byte aligned", q);
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(outs[q]), o1 = o0 + n * osz;
-        for (int m = 0; m < nmembers; ++m) {           // outputs are written before the redo pass
-            const uintptr_t p0 = reinterpret_cast<uintptr_t>(members[m]), p1 = p0 + n * isz;
-            if (p0 < o1 && o0 < p1) return fail(EDT_ERR_ARG, "output %d overlaps member %d", q, m);
-        }
-    }
+    bool todo;
+    int rc = check_population(check_speculative(n), members, nmembers, in_dt, pairs, npairs, outs, out_dt,
+                              nseg < 0 || nchunks < 0, nseg == 0 || nchunks == 0,
+                              !chunk_desc || !seg_first_chunk || !t || !partial || !coef || !redo, todo);
+    if (rc || !todo) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // the any-redo word (the workspace's last double): zeroed by the first pass, set by any child's
-    // coefficient kernel that sends a segment to the SLERP branch; clear, the redo grid exits at once
-    int32_t* any = reinterpret_cast<int32_t*>(partial + edt_slerp_population_speculative_doubles(npairs, nchunks) - 1);
-    // member-major form (r5: the needed layout; r4: the ring, EDT_POP_LAYOUT=ring): per component of
-    // the children's pair graph one pass reads each of its parents once, forms the component's
-    // needed sums (its norms + the dots its children use) AND writes every child's lerp-branch
-    // output from the members' registers (each distinct ordered pair computed once, stored to
-    // every child of it); then the children's coefficients from those sums and one member-major
-    // redo blend per component (which exits at once when no segment of any child needs the SLERP
-    // branch). Any pair graph over <= 8 distinct parents whose components fit their dot slots
-    // (every graph of <= 8 children) takes it; others the co-located pass below.
-    {
-        std::vector<int> compact(nmembers, -1), A(npairs), B(npairs);
-        const void* dm[kGramMaxMembers];
-        int D = 0;
-        bool fits = npairs <= kBlendMaxChildren;
-        for (int q = 0; q < npairs && fits; ++q)
-            for (int e = 0; e < 2 && fits; ++e) {
-                const int m = pairs[2 * q + e];
-                if (compact[m] < 0) {
-                    if (D == kGramMaxMembers) { fits = false; break; }
-                    compact[m] = D;
-                    dm[D++] = members[m];
-                }
-                (e ? B : A)[q] = compact[m];
-            }
-        GramPlan G;
-        if (fits) {
-            plan_gram(D, A.data(), B.data(), npairs, nchunks, G);
-            for (int k = 0; k < G.ncomp && fits; ++k) fits = G.kind[k] == kNeed;
+    int32_t* any = population_any_redo(partial, npairs, nchunks);
+    // member-major form (r5: the needed layout): per component of the children's pair graph one
+    // pass reads each of its parents once, forms the component's needed sums (its norms + the dots
+    // its children use) AND writes every child's lerp-branch output from the members' registers
+    // (each distinct ordered pair computed once, stored to every child of it); then the children's
+    // coefficients from those sums and one member-major redo blend per component (which exits at
+    // once when no segment of any child needs the SLERP branch). Any pair graph over <= 8 distinct
+    // parents whose components fit their dot slots and emit tables (every graph of <= 8 children)
+    // takes it (PopPlan::form); others the co-located pass below.
+    PopPlan P;
+    rc = population_plan(pairs, npairs, nmembers, nchunks, kPlanLaunch, P);
+    if (rc) return rc;
+    if (P.form == kFormMemberMajor) {
+        GramPlan& G = P.G;
+        P.bind_outputs(outs);
+        const Members dm = plan_members(P, members);
+        uint64_t scratch = 0;
+        for (int k = 0; k < G.ncomp; ++k) scratch += (uint64_t)nchunks * G.nt(k);
+        Members gm[kGramMaxMembers];
+        for (int k = 0; k < G.ncomp; ++k) {           // the passes first: only the first zeroes `any`
+            memset(&gm[k], 0, sizeof(Members));
+            for (int x = 0; x < G.size[k]; ++x) gm[k].p[x] = dm.p[G.list[k][x]];
+            G.need[k].t = t;
+            G.need[k].zero_word = k == 0 ? any : nullptr;
+            rc = need_sums(gm[k], G.size[k], G.need[k], in_dt, out_dt, true, chunk_desc, nchunks, partial + G.off[k],
+                           partial + scratch, s);
+            if (rc) return rc;
         }
-        if (fits) {                                     // each child onto its component's emit table
-            for (int q = 0; q < npairs && fits; ++q) {
-                const int k = G.comp_of[A[q]], n = G.size[k];
-                NeedSpec& S = G.need[k];
-                const int pa = G.pos[A[q]], pb = G.pos[B[q]];
-                int slot = -1;
-                void** first = nullptr;
-                uint32_t* bits = nullptr;
-                if (pa != pb && pb == (pa + 1) % n && (n >= 3 || pa == 0)) {
-                    slot = pa;
-                    bits = &S.fwd;
-                    first = &S.out_fwd[pa];
-                } else if (pa != pb && pa == (pb + 1) % n && (n >= 3 || pb == 0)) {
-                    slot = 8 + pb;
-                    bits = &S.rev;
-                    first = &S.out_rev[pb];
-                }
-                if (bits) {
-                    const uint32_t bit = 1u << (slot & 7);
-                    if (!(*bits & bit)) {
-                        *bits |= bit;
-                        *first = outs[q];
-                        continue;
-                    }
-                } else {                                // a chord or a self-pair: a picked pair
-                    int e = 0;
-                    while (e < S.nemit && !(S.ea[e] == pa && S.eb[e] == pb)) ++e;
-                    if (e == S.nemit) {
-                        if (e == kNeedChordEmits) { fits = false; break; }
-                        S.ea[e] = pa;
-                        S.eb[e] = pb;
-                        S.out[e] = outs[q];
-                        ++S.nemit;
-                        continue;
-                    }
-                    slot = 16 + e;
-                }
-                if (S.nextra == kNeedMaxOut) { fits = false; break; }   // a duplicate: same registers
-                S.xslot[S.nextra] = slot;
-                S.xout[S.nextra++] = outs[q];
-            }
-            for (int k = 0; k < G.ncomp; ++k) G.need[k].t = t;
+        for (int q = 0; q < npairs; ++q) {
+            rc = plan_child_coef(P, q, partial, seg_first_chunk, nseg, t, dot_threshold, eps, coef, dot_out, redo, any, s);
+            if (rc) return rc;
         }
-        if (fits) {
-            uint64_t scratch = 0;
-            for (int k = 0; k < G.ncomp; ++k) scratch += (uint64_t)nchunks * G.nt(k);
-            Members gm[kGramMaxMembers];
-            for (int k = 0; k < G.ncomp; ++k) {           // the passes first: only the first zeroes `any`
-                memset(&gm[k], 0, sizeof(Members));
-                for (int x = 0; x < G.size[k]; ++x) gm[k].p[x] = dm[G.list[k][x]];
-                G.need[k].zero_word = k == 0 ? any : nullptr;
-                int rc = need_sums(gm[k], G.size[k], G.need[k], in_dt, out_dt, true, chunk_desc, nchunks,
-                                   partial + G.off[k], partial + scratch, s);
-                if (rc) return rc;
-            }
+        for (int k = 0; k < G.ncomp; ++k) {
+            PopBlend pb;
+            memset(&pb, 0, sizeof(pb));
+            pb.any = any;
             for (int q = 0; q < npairs; ++q) {
-                const int k = G.comp_of[A[q]];
-                const int qd = G.dot_index(A[q], B[q]);
-                slerp_gram_coef_kernel<<<coef_grid(nseg), kBlock, 0, s>>>(
-                    partial + G.off[k], G.nt(k), G.norm_index(A[q]), G.norm_index(B[q]), qd, seg_first_chunk, nseg, t,
-                    (float)dot_threshold, (float)eps, coef + 2 * (size_t)nseg * q,
-                    dot_out ? dot_out + (size_t)nseg * q : nullptr, redo + (size_t)nseg * q, any);
-                int rc = check_launch("slerp_gram_coef_kernel");
-                if (rc) return rc;
+                if (G.comp_of[P.A[q]] != k) continue;
+                const auto c = child_slices(q, nseg, coef, nullptr, redo);
+                pb.out[pb.n] = outs[q];
+                pb.coef[pb.n] = c.coef;
+                pb.redo[pb.n] = c.redo;
+                pb.a[pb.n] = G.pos[P.A[q]];
+                pb.b[pb.n] = G.pos[P.B[q]];
+                ++pb.n;
             }
-            for (int k = 0; k < G.ncomp; ++k) {
-                PopBlend pb;
-                memset(&pb, 0, sizeof(pb));
-                pb.any = any;
-                for (int q = 0; q < npairs; ++q) {
-                    if (G.comp_of[A[q]] != k) continue;
-                    pb.out[pb.n] = outs[q];
-                    pb.coef[pb.n] = coef + 2 * (size_t)nseg * q;
-                    pb.redo[pb.n] = redo + (size_t)nseg * q;
-                    pb.a[pb.n] = G.pos[A[q]];
-                    pb.b[pb.n] = G.pos[B[q]];
-                    ++pb.n;
-                }
-                int rc = launch_blend_mm(gm[k], G.size[k], pb, in_dt, out_dt, chunk_desc, nchunks, s);
-                if (rc) return rc;
-            }
-            return EDT_OK;
+            rc = launch_blend_mm(gm[k], G.size[k], pb, in_dt, out_dt, chunk_desc, nchunks, s);
+            if (rc) return rc;
         }
+        return EDT_OK;
     }
+    // child q's chunk rows, and its level-0 row scratch after every child's rows
+    auto rows_of = [&](int q) { return partial + 3 * (size_t)nchunks * q; };
+    auto slots_of = [&](int q) { return rows_of(npairs) + 3 * (size_t)kPairRows * nchunks * q; };
     for (int pass = 0; pass < 2; ++pass) {
         for (int q0 = 0; q0 < npairs; q0 += kBlendMaxChildren) {
-            BlendChildren B;
-            memset(&B, 0, sizeof(B));
-            B.nchildren = npairs - q0 < kBlendMaxChildren ? npairs - q0 : kBlendMaxChildren;
-            for (int k = 0; k < B.nchildren; ++k) {
-                const int q = q0 + k;
-                B.v0[k] = members[pairs[2 * q]];
-                B.v1[k] = members[pairs[2 * q + 1]];
-                B.out[k] = outs[q];
-                B.coef[k] = coef + 2 * (size_t)nseg * q;
-                B.redo[k] = redo + (size_t)nseg * q;
-                B.slots[k] = partial + 3 * (size_t)nchunks * npairs + 3 * (size_t)kPairRows * nchunks * q;
-            }
+            BlendChildren B = colocated_group(members, pairs, npairs, outs, q0, nseg, coef, redo);
+            for (int k = 0; k < B.nchildren; ++k) B.slots[k] = slots_of(q0 + k);
             // pass 0: one block per (unit = 4 tiles of a chunk, child); pass 1: per (chunk, child)
             const uint64_t units = pass == 0 ? (uint64_t)nchunks * (kTileSlots / 4) : (uint64_t)nchunks;
-#define EDT_SPEC_POP(KERNEL, ...)                                                                   \
-    do {                                                                                            \
-        if (in_dt == EDT_F32 && out_dt == EDT_F32) KERNEL<EDT_F32, EDT_F32><<<gb, kBlock, 0, s>>>(__VA_ARGS__);   \
-        else if (in_dt == EDT_F32) KERNEL<EDT_F32, EDT_BF16><<<gb, kBlock, 0, s>>>(__VA_ARGS__);                  \
-        else if (out_dt == EDT_F32) KERNEL<EDT_BF16, EDT_F32><<<gb, kBlock, 0, s>>>(__VA_ARGS__);                 \
-        else KERNEL<EDT_BF16, EDT_BF16><<<gb, kBlock, 0, s>>>(__VA_ARGS__);                                       \
-    } while (0)
-            int rc = colocated_launches(units, B.nchildren, [&](uint64_t u0, unsigned gb) {
-                if (pass == 0) EDT_SPEC_POP(slerp_pop_stats_lerp_kernel, B, chunk_desc, nchunks, t, u0, any);
-                else EDT_SPEC_POP(slerp_blend_population_kernel, B, chunk_desc, nchunks, u0, any);
+            rc = colocated_launches(units, B.nchildren, [&](uint64_t u0, unsigned gb) {
+                with_io(in_dt, out_dt, [&](auto I, auto O) {
+                    constexpr int IDT = decltype(I)::value, ODT = decltype(O)::value;
+                    if (pass == 0)
+                        slerp_pop_stats_lerp_kernel<IDT, ODT><<<gb, kBlock, 0, s>>>(B, chunk_desc, nchunks, t, u0, any);
+                    else
+                        slerp_blend_population_kernel<IDT, ODT><<<gb, kBlock, 0, s>>>(B, chunk_desc, nchunks, u0, any);
+                    return 0;
+                });
             });
-#undef EDT_SPEC_POP
             if (rc) return rc;
         }
         if (pass == 0) {
             for (int q = 0; q < npairs; ++q) {
-                int rc = launch_tree_reduce(partial + 3 * (size_t)nchunks * npairs + 3 * (size_t)kPairRows * nchunks * q, 3,
-                                            kSpecWgRows ? kTileSlots / 4 : kPairRows, kTileSlots / 4,
-                                            kSpecWgRows ? 1 : kWavesPerBlock, nchunks,
-                                            partial + 3 * (size_t)nchunks * q, s);
+                rc = launch_tree_reduce(slots_of(q), 3, kSpecWgRows ? kTileSlots / 4 : kPairRows, kTileSlots / 4,
+                                        kSpecWgRows ? 1 : kWavesPerBlock, nchunks, rows_of(q), s);
                 if (rc) return rc;
-                slerp_coef_kernel<<<coef_grid(nseg), kBlock, 0, s>>>(
-                    partial + 3 * (size_t)nchunks * q, seg_first_chunk, nseg, t, (float)dot_threshold, (float)eps,
-                    coef + 2 * (size_t)nseg * q, dot_out ? dot_out + (size_t)nseg * q : nullptr, redo + (size_t)nseg * q,
-                    any);
+                const auto c = child_slices(q, nseg, coef, dot_out, redo);
+                slerp_coef_kernel<<<coef_grid(nseg), kBlock, 0, s>>>(rows_of(q), seg_first_chunk, nseg, t, (float)dot_threshold,
+                                                                     (float)eps, c.coef, c.dot, c.redo, any);
                 rc = check_launch("slerp_coef_kernel");
                 if (rc) return rc;
             }
@@ -2142,40 +2232,8 @@ int edt_slerp_population_speculative(const void* const* members, int nmembers, i
 // the table's rows are all-gathered, every rank forms every child's coefficients) ----
 
 namespace {
-// The distinct parents of `pairs` in first-use order (compact ids) and the GramPlan of the pair
-// graph: the same planning as edt_slerp_population, so a table row equals that pass's sums.
-struct NeededPlan {
-    int D = 0;
-    int orig[kGramMaxMembers];                 // compact -> member index
-    std::vector<int> A, B;                     // children's compact parents
-    GramPlan G;
-};
-
-int needed_plan(const int32_t* pairs, int npairs, int nmembers, int64_t nchunks, NeededPlan& P) {
-    if (nmembers < 1 || nmembers > kGramMaxMembers)
-        return fail(EDT_ERR_ARG, "member count %d out of range [1, %d]", nmembers, kGramMaxMembers);
-    if (npairs < 1 || !pairs) return fail(EDT_ERR_ARG, "no pairs");
-    if (nchunks < 0) return fail(EDT_ERR_ARG, "negative chunk count");
-    int compact[kGramMaxMembers];
-    for (int m = 0; m < nmembers; ++m) compact[m] = -1;
-    P.A.assign(npairs, 0);
-    P.B.assign(npairs, 0);
-    for (int q = 0; q < npairs; ++q)
-        for (int e = 0; e < 2; ++e) {
-            const int m = pairs[2 * q + e];
-            if (m < 0 || m >= nmembers) return fail(EDT_ERR_ARG, "pair %d: member out of range", q);
-            if (compact[m] < 0) {
-                compact[m] = P.D;
-                P.orig[P.D++] = m;
-            }
-            (e ? P.B : P.A)[q] = compact[m];
-        }
-    plan_gram(P.D, P.A.data(), P.B.data(), npairs, nchunks, P.G);
-    return EDT_OK;
-}
-
 // the two members (member indices) each column of block k holds the sum of
-void needed_columns(const NeededPlan& P, int k, int32_t* cols) {
+void needed_columns(const PopPlan& P, int k, int32_t* cols) {
     const GramPlan& G = P.G;
     const int M = G.size[k];
     const int* L = G.list[k];
@@ -2209,7 +2267,7 @@ int edt_slerp_needed_table(const int32_t* pairs, int npairs, int nmembers, int64
                            uint64_t* scratch_doubles) {
     g_err[0] = 0;
     if (!block_off || !block_nt || !ncomp || !table_doubles || !scratch_doubles) return fail(EDT_ERR_ARG, "null output");
-    NeededPlan P;
+    PopPlan P;
     int rc = needed_plan(pairs, npairs, nmembers, nchunks, P);
     if (rc) return rc;
     *ncomp = P.G.ncomp;
@@ -2232,7 +2290,7 @@ int edt_slerp_needed_sums(const void* const* members, int nmembers, int in_dt, c
                           double* table, double* scratch, uint64_t scratch_doubles, void* stream) {
     g_err[0] = 0;
     if (in_dt & ~1) return fail(EDT_ERR_ARG, "unsupported dtype");
-    NeededPlan P;
+    PopPlan P;
     int rc = needed_plan(pairs, npairs, nmembers, table_chunks, P);
     if (rc) return rc;
     if (nchunks < 0 || row0 < 0 || row0 + nchunks > table_chunks)
@@ -2243,13 +2301,9 @@ int edt_slerp_needed_sums(const void* const* members, int nmembers, int in_dt, c
     if (scratch_doubles < plan_row_scratch(P.G, nchunks))
         return fail(EDT_ERR_ARG, "scratch of %llu doubles, the passes need %llu", (unsigned long long)scratch_doubles,
                     (unsigned long long)plan_row_scratch(P.G, nchunks));
-    Members mem;
-    memset(&mem, 0, sizeof(mem));
-    for (int d = 0; d < P.D; ++d) {
-        const void* m = members[P.orig[d]];
-        if (!m || !aligned16(m)) return fail(EDT_ERR_ARG, "member %d is null or not 16-byte aligned", P.orig[d]);
-        mem.p[d] = m;
-    }
+    const Members mem = plan_members(P, members);          // only the parents in use are read
+    for (int d = 0; d < P.D; ++d)
+        if (!mem.p[d] || !aligned16(mem.p[d])) return fail(EDT_ERR_ARG, "member %d is null or not 16-byte aligned", P.orig[d]);
     for (int k = 0; k < P.G.ncomp; ++k) {
         // rows [row0, row0 + nchunks) of the component's block (plan_component_sums adds the
         // block's offset)
@@ -2264,21 +2318,15 @@ int edt_slerp_needed_coef(const double* table, int64_t table_chunks, const int32
                           const int32_t* seg_first_chunk, int nseg, const double* t, double dot_threshold, double eps,
                           float* coef, float* dot_out, void* stream) {
     g_err[0] = 0;
-    NeededPlan P;
+    PopPlan P;
     int rc = needed_plan(pairs, npairs, nmembers, table_chunks, P);
     if (rc) return rc;
     if (nseg < 0) return fail(EDT_ERR_ARG, "negative count");
     if (nseg == 0) return EDT_OK;
     if (!table || !seg_first_chunk || !t || !coef) return fail(EDT_ERR_ARG, "null buffer");
-    hipStream_t s = (hipStream_t)stream;
     for (int q = 0; q < npairs; ++q) {
-        const int i = P.A[q], j = P.B[q];
-        const int k = P.G.comp_of[i];
-        slerp_gram_coef_kernel<<<coef_grid(nseg), kBlock, 0, s>>>(
-            table + P.G.off[k], P.G.nt(k), P.G.norm_index(i), P.G.norm_index(j), P.G.dot_index(i, j), seg_first_chunk,
-            nseg, t, (float)dot_threshold, (float)eps, coef + 2 * (size_t)nseg * q,
-            dot_out ? dot_out + (size_t)nseg * q : nullptr);
-        rc = check_launch("slerp_gram_coef_kernel");
+        rc = plan_child_coef(P, q, table, seg_first_chunk, nseg, t, dot_threshold, eps, coef, dot_out, nullptr, nullptr,
+                             (hipStream_t)stream);
         if (rc) return rc;
     }
     return EDT_OK;
@@ -2291,63 +2339,25 @@ int edt_slerp_population_layout(const int32_t* pairs, int npairs, int nmembers, 
     if (!buf || buflen < 2) return fail(EDT_ERR_ARG, "null or short buffer");
     if (npairs < 0 || nmembers < 1) return fail(EDT_ERR_ARG, "bad count");
     if (npairs > 0 && !pairs) return fail(EDT_ERR_ARG, "null pairs");
-    std::vector<int> compact(nmembers, -1), orig, A(npairs), B(npairs);
-    for (int q = 0; q < npairs; ++q)
-        for (int e = 0; e < 2; ++e) {
-            const int m = pairs[2 * q + e];
-            if (m < 0 || m >= nmembers) return fail(EDT_ERR_ARG, "pair %d: member out of range", q);
-            if (compact[m] < 0) {
-                compact[m] = (int)orig.size();
-                orig.push_back(m);
-            }
-            (e ? B : A)[q] = compact[m];
-        }
-    const int D = (int)orig.size();
-    std::string js = "{\"distinct_parents\": " + std::to_string(D) + ", \"children\": " + std::to_string(npairs);
-    if (D > kGramMaxMembers) {
-        js += std::string(", \"form\": \"") + (speculate ? "co-located" : "unsupported") + "\", \"components\": []}";
-    } else {
-        GramPlan G;
-        plan_gram(D, A.data(), B.data(), npairs, 1, G);
-        bool mm = npairs <= kBlendMaxChildren;
-        std::string comps;
-        for (int k = 0; k < G.ncomp; ++k) {
-            const int n = G.size[k];
-            int nemit = 0, picked = 0, ea[64], eb[64];
-            for (int q = 0; q < npairs; ++q) {        // distinct ordered pairs; those off the ring
-                if (G.comp_of[A[q]] != k) continue;
-                int e = 0;
-                while (e < nemit && !(ea[e] == A[q] && eb[e] == B[q])) ++e;
-                if (e < nemit || nemit == 64) continue;
-                ea[nemit] = A[q];
-                eb[nemit++] = B[q];
-                const int pa = G.pos[A[q]], pb = G.pos[B[q]];
-                picked += !(G.kind[k] == kNeed && pa != pb && GramPlan::ring_edge(pa, pb, n) >= 0);
-            }
-            int dupes = 0;
-            for (int q = 0; q < npairs; ++q) dupes += G.comp_of[A[q]] == k;
-            dupes -= nemit;
-            mm = mm && G.kind[k] == kNeed && picked <= kNeedChordEmits && dupes <= kNeedMaxOut;
-            int ndots = 0;
-            for (int q = 0; q < npairs; ++q) {     // distinct unordered dots of the component
-                if (G.comp_of[A[q]] != k || A[q] == B[q]) continue;
-                bool seen = false;
-                for (int r = 0; r < q; ++r)
-                    seen = seen || (G.comp_of[A[r]] == k && ((A[r] == A[q] && B[r] == B[q]) || (A[r] == B[q] && B[r] == A[q])));
-                ndots += !seen;
-            }
-            std::string mem;
-            for (int x = 0; x < G.size[k]; ++x) mem += (x ? ", " : "") + std::to_string(orig[G.list[k][x]]);
-            const char* kind = G.kind[k] == kNeed ? "needed" : "triangle";
-            const int chords = G.kind[k] == kNeed ? G.need[k].nchord : 0;
-            comps += std::string(k ? ", " : "") + "{\"members\": [" + mem + "], \"dots\": " + std::to_string(ndots) +
-                     ", \"chords\": " + std::to_string(chords) + ", \"sums\": " + std::to_string(G.nt(k)) +
-                     ", \"stats_layout\": \"" + kind + "\", \"emit_pairs\": " + std::to_string(nemit) +
-                     ", \"picked_pairs\": " + std::to_string(picked) + "}";
-        }
-        const char* form = speculate ? (mm ? "member-major" : "co-located") : "two-pass";
-        js += std::string(", \"form\": \"") + form + "\", \"components\": [" + comps + "]}";
+    PopPlan P;
+    int rc = population_plan(pairs, npairs, nmembers, 1, kPlanReport, P);
+    if (rc) return rc;
+    const GramPlan& G = P.G;
+    const char* form = speculate ? (P.form == kFormMemberMajor ? "member-major" : "co-located")
+                                 : (P.planned ? "two-pass" : "unsupported");
+    std::string comps;
+    for (int k = 0; P.planned && k < G.ncomp; ++k) {
+        std::string mem;
+        for (int x = 0; x < G.size[k]; ++x) mem += (x ? ", " : "") + std::to_string(P.orig[G.list[k][x]]);
+        const char* kind = G.kind[k] == kNeed ? "needed" : "triangle";
+        const int chords = G.kind[k] == kNeed ? G.need[k].nchord : 0;
+        comps += std::string(k ? ", " : "") + "{\"members\": [" + mem + "], \"dots\": " + std::to_string(P.ndots[k]) +
+                 ", \"chords\": " + std::to_string(chords) + ", \"sums\": " + std::to_string(G.nt(k)) +
+                 ", \"stats_layout\": \"" + kind + "\", \"emit_pairs\": " + std::to_string(P.npair[k]) +
+                 ", \"picked_pairs\": " + std::to_string(P.npicked[k]) + "}";
     }
+    const std::string js = "{\"distinct_parents\": " + std::to_string(P.D) + ", \"children\": " + std::to_string(npairs) +
+                           ", \"form\": \"" + form + "\", \"components\": [" + comps + "]}";
     if ((int)js.size() + 1 > buflen) return fail(EDT_ERR_ARG, "buffer of %d bytes too short (%d)", buflen, (int)js.size() + 1);
     memcpy(buf, js.c_str(), js.size() + 1);
     return EDT_OK;
@@ -2379,23 +2389,6 @@ bool spans_apart(std::vector<Span>& sp) {
         if (x.e > f) f = x.e;
     }
     return true;
-}
-
-// the redo blends / any table blend with a redo mask: grid-stride over chunks (most are skipped)
-int blend_redo(const void* v0, const void* v1, int in_dt, void* out, int out_dt, const uint64_t* chunk_desc,
-               int64_t nchunks, const float* coef, const uint64_t* seg_ptrs, const int32_t* redo,
-               const int32_t* any, hipStream_t s) {
-    const unsigned g = slerp_spec_grid(nchunks);
-    constexpr bool kNtB = EDT_NT_SLERP != 0;
-    if (in_dt == EDT_F32 && out_dt == EDT_F32)
-        slerp_blend_kernel<EDT_F32, EDT_F32, false><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, seg_ptrs, redo, any);
-    else if (in_dt == EDT_F32)
-        slerp_blend_kernel<EDT_F32, EDT_BF16, false><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, seg_ptrs, redo, any);
-    else if (out_dt == EDT_F32)
-        slerp_blend_kernel<EDT_BF16, EDT_F32, kNtB><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, seg_ptrs, redo, any);
-    else
-        slerp_blend_kernel<EDT_BF16, EDT_BF16, kNtB><<<g, kBlock, 0, s>>>(v0, v1, out, chunk_desc, nchunks, coef, seg_ptrs, redo, any);
-    return check_launch("slerp_blend_kernel");
 }
 
 int table_args(const uint64_t* table, int in_dt, int out_dt, int64_t nchunks, int nseg) {
@@ -2576,8 +2569,7 @@ int edt_slerp_merge_table_speculative(const uint64_t* seg_table, int in_dt, int 
     if (nseg == 0 || nchunks == 0) return EDT_OK;
     if (!chunk_desc || !seg_first_chunk || !t || !partial || !coef || !redo) return fail(EDT_ERR_ARG, "null buffer");
     hipStream_t s = (hipStream_t)stream;
-    // the any-redo word: the last double of the workspace, as edt_slerp_merge_speculative's
-    int32_t* any = reinterpret_cast<int32_t*>(partial + edt_slerp_sums_doubles(3, nchunks) - 1);
+    int32_t* any = pair_any_redo(partial, nchunks);
     rc = pair_sums(nullptr, nullptr, in_dt, nullptr, out_dt, true, chunk_desc, nchunks, partial, t, seg_table, s, any);
     if (rc) return rc;
     slerp_coef_kernel<<<coef_grid(nseg), kBlock, 0, s>>>(partial, seg_first_chunk, nseg, t, (float)dot_threshold,
@@ -2667,26 +2659,21 @@ static int refdot_impl(const void* v0, const void* v1, int in_dt, const uint64_t
     const int bpc = (int)(chunk_elems / kRefBuf);
     const uint64_t gn = 2ull * (uint64_t)nseg * (uint64_t)threads;
     if (gn > kGridBlockCap) return fail(EDT_ERR_ARG, "too many segments x threads");
-    if (in_dt == EDT_F32)
-        refdot_norm_kernel<EDT_F32><<<(unsigned)gn, kRefThreads, 0, s>>>(v0, v1, chunk_desc, seg_first_chunk, nseg, flag,
-                                                                         threads, seg_ptrs, part);
-    else
-        refdot_norm_kernel<EDT_BF16><<<(unsigned)gn, kRefThreads, 0, s>>>(v0, v1, chunk_desc, seg_first_chunk, nseg,
-                                                                          flag, threads, seg_ptrs, part);
-    int rc = check_launch("refdot_norm_kernel");
+    int rc = with_dtype(in_dt, [&](auto I) {
+        refdot_norm_kernel<decltype(I)::value><<<(unsigned)gn, kRefThreads, 0, s>>>(v0, v1, chunk_desc, seg_first_chunk, nseg,
+                                                                                  flag, threads, seg_ptrs, part);
+        return check_launch("refdot_norm_kernel");
+    });
     if (rc) return rc;
     if (nchunks > 0) {
         const uint64_t waves = (uint64_t)nchunks * (uint64_t)bpc;
         const uint64_t gs = (waves + kBlock / 64 - 1) / (kBlock / 64);
         if (gs > kGridBlockCap) return fail(EDT_ERR_ARG, "too many chunks for one launch");
-        if (in_dt == EDT_F32)
-            refdot_sum_kernel<EDT_F32><<<(unsigned)gs, kBlock, 0, s>>>(v0, v1, chunk_desc, nchunks, seg_first_chunk, flag,
-                                                                        threads, (float)eps, seg_ptrs, part, bpc, bsum);
-        else
-            refdot_sum_kernel<EDT_BF16><<<(unsigned)gs, kBlock, 0, s>>>(v0, v1, chunk_desc, nchunks, seg_first_chunk,
-                                                                         flag, threads, (float)eps, seg_ptrs, part, bpc,
-                                                                         bsum);
-        rc = check_launch("refdot_sum_kernel");
+        rc = with_dtype(in_dt, [&](auto I) {
+            refdot_sum_kernel<decltype(I)::value><<<(unsigned)gs, kBlock, 0, s>>>(
+                v0, v1, chunk_desc, nchunks, seg_first_chunk, flag, threads, (float)eps, seg_ptrs, part, bpc, bsum);
+            return check_launch("refdot_sum_kernel");
+        });
         if (rc) return rc;
     }
     refdot_total_kernel<<<(unsigned)((nseg + kBlock - 1) / kBlock), kBlock, 0, s>>>(chunk_desc, seg_first_chunk, nseg,

@@ -1,16 +1,14 @@
 // edt_step.h — the one text of the outer step's pieces that the fused kernels (edt_outer.hip) and
 // the quantized sharded kernels (edt_quant.hip) both run: a worker's delta added to the sum, the
 // rank-ordered sum of partials and the SGD step from it, the two grid-stride drivers, and the host
-// side's runtime-code -> compile-time-tag dispatch. Their bit-for-bit agreement across the fp32
-// and the quantized schedules rests on this file: a variant of the step is written here once.
+// checks the sharded entries share (the runtime-code -> compile-time-tag dispatch is edt_common.h's,
+// with every unit's). Their bit-for-bit agreement across the fp32 and the quantized schedules rests
+// on this file: a variant of the step is written here once.
 #pragma once
 
 #include "edt_common.h"
 
 namespace {
-
-template <int V> using Int = std::integral_constant<int, V>;
-template <bool V> using Bool = std::integral_constant<bool, V>;
 
 // ---------------------------------------------------------------------------------------
 // grid-stride drivers
@@ -164,48 +162,6 @@ __device__ __forceinline__ void st_bcast(const BcastDst& d, uint64_t i, const fl
 }
 
 // ---------------------------------------------------------------------------------------
-// host dispatch: a runtime code picks the compile-time tag the generic lambda f is called with
-// (the entries have validated the codes), so a launch site is one nested call
-
-template <class F>
-int with_pair(int gdt, int wdt, F&& f) {            // (master, worker) dtype: valid_pair's three
-    if (gdt == EDT_F32 && wdt == EDT_F32) return f(Int<EDT_F32>{}, Int<EDT_F32>{});
-    if (gdt == EDT_F32) return f(Int<EDT_F32>{}, Int<EDT_BF16>{});
-    return f(Int<EDT_BF16>{}, Int<EDT_BF16>{});
-}
-
-template <class F>
-int with_dtype(int gdt, F&& f) {
-    return gdt == EDT_F32 ? f(Int<EDT_F32>{}) : f(Int<EDT_BF16>{});
-}
-
-template <class F>
-int with_fmt(int fmt, F&& f) {
-    return fmt == EDT_MXFP8 ? f(Int<EDT_MXFP8>{}) : f(Int<EDT_MXFP4>{});
-}
-
-template <class F>
-int with_bool(bool b, F&& f) {
-    return b ? f(Bool<true>{}) : f(Bool<false>{});
-}
-
-// (KC, DIV): compile-time worker counts for the common populations of a table, else the generic
-// loop (KC = 0, also what K = 0 asks for); the divisor is K_total. KC_FUSED (the fused and list
-// kernels): 1, 2, 4, 8 with the multiply, 3 with the division; KC_QUANT (the quantized partial): 8.
-enum { KC_QUANT = 0, KC_FUSED = 1 };
-template <int TABLE, class F>
-int with_kc_div(int K, bool div_exact, F&& f) {
-    if constexpr (TABLE == KC_FUSED) {
-        if (K == 1 && !div_exact) return f(Int<1>{}, Int<0>{});
-        if (K == 2 && !div_exact) return f(Int<2>{}, Int<0>{});
-        if (K == 3 && div_exact) return f(Int<3>{}, Int<1>{});
-        if (K == 4 && !div_exact) return f(Int<4>{}, Int<0>{});
-    }
-    if (K == 8 && !div_exact) return f(Int<8>{}, Int<0>{});
-    return div_exact ? f(Int<0>{}, Int<1>{}) : f(Int<0>{}, Int<0>{});
-}
-
-// ---------------------------------------------------------------------------------------
 // host validation shared by the sharded entries (same codes, same messages)
 
 inline int check_master_dtype(int gdt) {
@@ -250,11 +206,6 @@ inline int check_bcast_count(int nbcast) {
     if (nbcast < 0 || nbcast > EDT_MAX_WORKERS)
         return fail(EDT_ERR_ARG, "broadcast count %d out of range [0, %d]", nbcast, EDT_MAX_WORKERS);
     return EDT_OK;
-}
-
-inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
 }
 
 // d = bcast[0 .. nbcast) (nbcast >= 1, n != 0 elements of wdt each): each checked non-null and

@@ -301,17 +301,29 @@ def test_pair_merge_golden(golden, oracle, dev, ops, idx):
 @pytest.mark.parametrize("in_dt,cdt,out_dt", [(torch.float32, torch.float32, torch.float32),
                                               (torch.bfloat16, torch.bfloat16, torch.bfloat16),
                                               (torch.bfloat16, torch.float32, torch.float32),
-                                              (torch.bfloat16, torch.float32, torch.bfloat16)])
+                                              (torch.bfloat16, torch.float32, torch.bfloat16),
+                                              (torch.float32, torch.float32, torch.bfloat16),
+                                              (torch.bfloat16, torch.bfloat16, torch.float32)])
 @pytest.mark.parametrize("t", [0.0, 0.5, 0.43333333333333335, 1.0])
 def test_lerp_vs_oracle(oracle, dev, ops, in_dt, cdt, out_dt, t):
+    """edt_lerp's six legal (input, compute, output) triples (fp32 inputs compute in fp32 only), each
+    over 16-byte-aligned buffers (the 8-element body + tail) and over views 4 bytes off (the scalar
+    body): bit-exact against the oracle."""
     g = torch.Generator().manual_seed(3)
     n = 70_001
     v0 = (torch.randn(n, generator=g) * 0.02).to(in_dt)
     v1 = (torch.randn(n, generator=g) * 0.02).to(in_dt)
-    out_d = torch.empty(n, dtype=out_dt, device=dev)
-    ops.lerp(t, v0.to(dev), v1.to(dev), out=out_d, compute_dtype=cdt)
     want = oracle.lerp(t, v0, v1, compute_dtype=cdt, out_dtype=out_dt)
-    assert torch.equal(bits(out_d.cpu()), bits(want))
+    for shifted in (False, True):
+        def place(x):                                   # a device copy at offset 0 or 4 bytes
+            k = 4 // x.element_size() if shifted else 0
+            buf = torch.empty(x.numel() + k, dtype=x.dtype, device=dev)
+            buf[k:].copy_(x)
+            return buf[k:]
+        out_d = place(torch.zeros(n, dtype=out_dt))
+        assert (out_d.data_ptr() % 16 == 4) == shifted
+        ops.lerp(t, place(v0), place(v1), out=out_d, compute_dtype=cdt)
+        assert torch.equal(bits(out_d.cpu()), bits(want)), shifted
 
 
 def _slerp_tol(c0, c1, v0, v1):
@@ -592,6 +604,48 @@ def test_slerp_population_pair_graphs_dtypes(dev, ops, graph, in_dt, out_dt):
             ops.slerp_arena(plan, mem[i], mem[j], want, ts, speculate=False)
             assert torch.equal(bits(outs[q].cpu()), bits(want.cpu())), (graph, speculate, q)
             assert torch.equal(dots[q].cpu(), plan.dots[:len(sizes)].cpu()), (graph, speculate, q)
+
+
+_POP_ARM_GRAPHS = {
+    # 3 members, a self-pair and a duplicate child: one component, member-major in both forms
+    "three_members": (3, [(0, 1), (1, 2), (2, 2), (0, 1), (2, 0)], (False, True)),
+    # 17 children: past one member-major launch, the co-located blends (two-pass) and the
+    # co-located speculative passes
+    "seventeen_children": (4, [(c % 4, (c + 1 + c // 4) % 4) for c in range(17)], (False, True)),
+    # 9 distinct parents: the speculative entry's co-located fallback (the two-pass form refuses)
+    "nine_parents": (9, [(m, (m + 1) % 9) for m in range(9)], (True,)),
+}
+
+
+@pytest.mark.parametrize("in_dt,out_dt", [(torch.float32, torch.float32), (torch.float32, torch.bfloat16),
+                                          (torch.bfloat16, torch.float32), (torch.bfloat16, torch.bfloat16)])
+@pytest.mark.parametrize("graph", sorted(_POP_ARM_GRAPHS))
+def test_slerp_population_every_dtype_arm(dev, ops, graph, in_dt, out_dt):
+    """Every (input, output) dtype arm of the population launch sites — the needed-sums pass with and
+    without outputs, the member-major blends, the co-located blends and the co-located speculative
+    passes — at a small shape: a 1-element segment and one of 65,536 + 513 elements (a chunk
+    boundary, a partial tile, a tail under 8 elements). Every child is bit-identical to the
+    two-pass pair merge, sums' dots included (the canonical chunk-sum order)."""
+    nmem, pairs, forms = _POP_ARM_GRAPHS[graph]
+    offs = [0, 1, 1 + 65_536 + 513]
+    g = torch.Generator().manual_seed(97 + nmem)
+    base = torch.randn(offs[-1], generator=g) * 0.02
+    # members 0 and 1 near each other (the lerp branch), the others farther (the SLERP branch, the redo)
+    mem = [(base + torch.randn(offs[-1], generator=g) * (1e-5 if m < 2 else 1e-3) * (m + 1)).to(in_dt).to(dev)
+           for m in range(nmem)]
+    ts = torch.tensor([0.25, 0.6], dtype=torch.float64).to(dev)
+    plan = ops.make_slerp_plan(offs, dev)
+    want, want_dots = {}, {}
+    for i, j in set(pairs):
+        want[i, j] = torch.empty(offs[-1], dtype=out_dt, device=dev)
+        ops.slerp_arena(plan, mem[i], mem[j], want[i, j], ts, speculate=False)
+        want_dots[i, j] = plan.dots[:2].clone()
+    for speculate in forms:
+        outs = [torch.full((offs[-1],), float("nan"), dtype=out_dt, device=dev) for _ in pairs]
+        dots = ops.slerp_population(plan, mem, pairs, outs, ts, speculate=speculate).clone()
+        for q, p in enumerate(pairs):
+            assert torch.equal(bits(outs[q].cpu()), bits(want[p].cpu())), (graph, speculate, q, p)
+            assert torch.equal(dots[q].cpu(), want_dots[p].cpu()), (graph, speculate, q, p)
 
 
 @pytest.mark.parametrize("threads,vec", [(1, 32), (8, 32), (3, 16)])
