@@ -137,6 +137,23 @@ constexpr bool split_halves() {
 #define EDT_MIN_WAVES 1
 #endif
 
+// Workgroups resident per CU for the fp32 fused step at K = 8 with a carried momentum buffer
+// (outer_kernel, and probe_kernel in that regime; edt_outer.hip's window_capped says exactly which
+// launches); 0 = uncapped, i.e. what the body's registers allow. With the one-pass grid the chip
+// holds (resident workgroups) x 8 KB of each of the step's 10 buffers in flight (8 read, 2 read and
+// rewritten), and the rate falls as that window widens (profiles/HISTORY.md §D). The cap is a
+// dynamic-LDS request of 160 KB / cap that the kernels never touch, so their code is the same for
+// every value.
+#ifndef EDT_OUTER_WG_PER_CU
+#define EDT_OUTER_WG_PER_CU 1
+#endif
+static_assert(EDT_OUTER_WG_PER_CU >= 0 && EDT_OUTER_WG_PER_CU <= 8 && EDT_OUTER_WG_PER_CU != 7,
+              "EDT_OUTER_WG_PER_CU: 0 (uncapped), 1-6 or 8");
+// rounded down to 5 KB (a multiple of the LDS allocation granule): cap x bytes <= 160 KB < (cap + 1) x bytes
+// for caps 1-6 and 8
+constexpr size_t kOuterWindowLds =
+    EDT_OUTER_WG_PER_CU > 0 ? (size_t)160 * 1024 / EDT_OUTER_WG_PER_CU / 5120 * 5120 : 0;
+
 constexpr int kBlock = 256;                         // 4 waves
 constexpr int kVec = 8;                             // elements per thread per iteration
 // HIP's dispatch limit: at most 2^32 - 1 work-items per grid dimension, i.e. 16,777,215 workgroups

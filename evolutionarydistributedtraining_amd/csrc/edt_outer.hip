@@ -4,6 +4,7 @@
 #include "edt_step.h"
 
 #include <algorithm>
+#include <atomic>
 
 namespace {
 
@@ -413,6 +414,40 @@ __global__ __launch_bounds__(kBlock) void broadcast_theta_kernel(const void* the
 // ---------------------------------------------------------------------------------------
 // launch helpers
 
+// The in-flight window of the fp32 fused step (EDT_OUTER_WG_PER_CU, edt_common.h): the launch's
+// dynamic-LDS bytes for kernel KERN, which never touches them. Only the mix that was measured is
+// capped: fp32 master and workers, K = 8 (the compile-time body), the 8-element split-halves form,
+// plain fused mode (no broadcast, no clip), and — at run time — a carried momentum buffer, i.e. 8
+// buffers read and 2 read and rewritten. Every other instantiation launches as it did.
+template <int GDT, int WDT, int KC, int MODE, int N, bool BC, bool SC>
+constexpr bool window_capped() {
+    return GDT == EDT_F32 && WDT == EDT_F32 && KC == 8 && MODE == MODE_FUSED && N == kVec && !BC && !SC &&
+           split_halves<GDT, WDT>();
+}
+// A request above 64 KB is raised for the kernel once per device (the attribute belongs to the
+// current one); where the runtime refuses, the launch is uncapped.
+template <auto KERN>
+size_t window_lds() {
+    if constexpr (kOuterWindowLds > 64 * 1024) {
+        constexpr int kMaxDev = 64;
+        static std::atomic<signed char> state[kMaxDev];      // 0 not asked, 1 raised, -1 refused
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        signed char st = state[dev].load(std::memory_order_relaxed);
+        if (st == 0) {
+            st = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)kOuterWindowLds) == hipSuccess ? 1 : -1;
+            if (st < 0) (void)hipGetLastError();
+            state[dev].store(st, std::memory_order_relaxed);
+        }
+        if (st < 0) return 0;
+    }
+    return kOuterWindowLds;
+}
+
 template <int MODE, bool BC = false, bool SC = false>
 int launch_outer(int gdt, int wdt, const OuterArgs& a, bool vec, hipStream_t s) {
     const unsigned g = grid_for(a.n, vec);
@@ -421,8 +456,12 @@ int launch_outer(int gdt, int wdt, const OuterArgs& a, bool vec, hipStream_t s) 
         return with_kc_div<KC_FUSED>(kc, a.div_exact, [&](auto KC, auto DIV) {
             return with_bool(vec, [&](auto V) {
                 constexpr int N = decltype(V)::value ? kVec : 1;
-                outer_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value, decltype(DIV)::value, MODE, N, BC, SC>
-                    <<<g, kBlock, 0, s>>>(a);
+                constexpr int GD = decltype(G)::value, WD = decltype(W)::value;
+                constexpr auto kern = outer_kernel<GD, WD, decltype(KC)::value, decltype(DIV)::value, MODE, N, BC, SC>;
+                size_t lds = 0;
+                if constexpr (window_capped<GD, WD, decltype(KC)::value, MODE, N, BC, SC>())
+                    if (a.sgd.use_momentum && a.sgd.has_buf) lds = window_lds<kern>();
+                kern<<<g, kBlock, lds, s>>>(a);
                 return check_launch("outer_kernel");
             });
         });
@@ -528,7 +567,12 @@ int edt_probe_stream(void* theta_g, int gdt, const void* const* theta_k, int wdt
     hipStream_t s = (hipStream_t)stream;
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_bool(K == 8, [&](auto K8) {
-            probe_kernel<decltype(G)::value, decltype(W)::value, decltype(K8)::value ? 8 : 0><<<g, kBlock, 0, s>>>(a);
+            constexpr int GD = decltype(G)::value, WD = decltype(W)::value;
+            constexpr auto kern = probe_kernel<GD, WD, decltype(K8)::value ? 8 : 0>;
+            size_t lds = 0;                                  // the step's window, so the ceiling tracks the kernel
+            if constexpr (window_capped<GD, WD, decltype(K8)::value ? 8 : 0, MODE_FUSED, kVec, false, false>())
+                lds = window_lds<kern>();
+            kern<<<g, kBlock, lds, s>>>(a);
             return check_launch("probe_kernel");
         });
     });
