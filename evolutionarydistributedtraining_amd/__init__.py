@@ -11,10 +11,11 @@ from ._lib import EdtError, load_library
 from .diloco import DILOCO_DEFAULTS, DILOCO_SIM_DEFAULTS, OuterState, OuterSync, outer_step, outer_step_fragment
 from .fragments import FragmentPlan
 from .params import ParamArena, ParamLayout, arena_of_module, bind_module_
+from .sharded_fragments import ShardedFragmentSync
 
 __all__ = [
     "EdtError", "load_library", "OuterState", "OuterSync", "outer_step", "DILOCO_DEFAULTS",
     "DILOCO_SIM_DEFAULTS", "ParamArena", "ParamLayout", "arena_of_module", "bind_module_",
-    "FragmentPlan", "outer_step_fragment",
+    "FragmentPlan", "outer_step_fragment", "ShardedFragmentSync",
 ]
 __version__ = "0.1.0"

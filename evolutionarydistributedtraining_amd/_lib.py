@@ -61,6 +61,15 @@ SIGNATURES = [
     ("edt_sgd_apply_sum", _I, [_P, _I, ctypes.POINTER(_P), _I, _P, _I, _U64, _D, _D, _I, _P]),
     ("edt_sgd_apply_scaled", _I, [_P, _I, _P, _P, _I, _U64, _D, _D, _I, ctypes.c_float, _P]),
     ("edt_sgd_apply_sum_scaled", _I, [_P, _I, ctypes.POINTER(_P), _I, _P, _I, _U64, _D, _D, _I, ctypes.c_float, _P]),
+    ("edt_delta_partial_list_workspace_bytes", _U64, [_I, _I]),
+    ("edt_delta_partial_list", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, _I, _I, ctypes.POINTER(_P),
+                                    ctypes.POINTER(_U64), _I, _P, _U64, _P]),
+    ("edt_sgd_sum_list_to_workspace_bytes", _U64, [_I, _I]),
+    ("edt_sgd_sum_list_to", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I,
+                                 ctypes.POINTER(_P), ctypes.POINTER(_U64), _I, _D, _D, _I, _P, _U64, _P]),
+    ("edt_theta_scatter_mix_list_workspace_bytes", _U64, [_I, _I]),
+    ("edt_theta_scatter_mix_list", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), ctypes.POINTER(_P), _I, _I, _D,
+                                        ctypes.POINTER(_U64), _I, _P, _U64, _P]),
     ("edt_partial_sum_stats_doubles", _U64, [ctypes.c_int64]),
     ("edt_partial_sum_stats", _I, [ctypes.POINTER(_P), _I, _I, _U64, _P, ctypes.c_int64, _P, _P]),
     ("edt_q_region_bytes", _U64, [_U64, _I]),

@@ -99,6 +99,20 @@ class FragmentPlan:
         """The fragment's tensors in arena order, adjacent ones coalesced: (offset, numel) runs."""
         return list(self._runs[p])
 
+    def pieces(self, p: int, lo: int, hi: int) -> list[tuple[int, int, int]]:
+        """Fragment space is fragment p's runs laid back to back (the layout of its snapshots). The
+        sub-runs covered by the fragment-space range [lo, hi), in that order, as (arena offset,
+        fragment-space offset, numel): runs are cut at the range's bounds, empty pieces are left
+        out, and the part of the range at or beyond numel(p) (the padding of a sharded fragment)
+        has none."""
+        out, off = [], 0
+        for a, n in self._runs[p]:
+            s, e = max(lo, off), min(hi, off + n)
+            if s < e:
+                out.append((a + s - off, s, e - s))
+            off += n
+        return out
+
     def views(self, p: int, flat: torch.Tensor) -> list[torch.Tensor]:
         """The run views of a flat buffer laid out by the plan's layout."""
         if flat.numel() != self.layout.total:

@@ -322,6 +322,127 @@ def _outer_step_list(thetas, workers, momenta, has_momentum, lr, momentum_coef, 
         L.check(lib.edt_outer_step_list_tail(*head, L.ptr(bits), toff, *tail), "edt_outer_step_list_tail")
 
 
+# The sharded fragment step's three phases over piece lists (sharded_fragments.py). A piece is one
+# contiguous stretch of every operand: thetas[t], workers[k][t], ... are T views of the same sizes,
+# into arenas or into compact fragment-space buffers, at any element offset.
+
+def _piece_columns(name: str, lists, numels, dtype, dev) -> list[torch.Tensor]:
+    """Further operand lists of a piece-list entry (each one tensor per piece): flat, checked like
+    `_check_list_operands` checks its own — device, contiguity, one dtype, the pieces' sizes."""
+    flat = [t for l in lists for t in l]
+    if any(len(l) != len(numels) for l in lists):
+        raise L.EdtError(f"{name}: one tensor per piece")
+    if not all([t.is_cuda and t.is_contiguous() and t.device == dev for t in flat]):
+        raise L.EdtError(f"{name} must be contiguous tensors on the operands' device")
+    if any(t.dtype != dtype for t in flat) or any([t.numel() for t in l] != numels for l in lists):
+        raise L.EdtError(f"{name} must have dtype {dtype} and the pieces' sizes")
+    return flat
+
+
+def _ptrs(tensors):
+    return (ctypes.c_void_p * max(1, len(tensors)))(*[t.data_ptr() for t in tensors])
+
+
+def delta_partial_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]], k_total: int,
+                       accs: list[torch.Tensor]) -> None:
+    """`delta_partial` over T pieces in ONE launch (edt_delta_partial_list): accs[t] (fp32) = the sum
+    over the local workers, in order, of round((workers[k][t] - thetas[t]) / k_total) — bit for bit
+    what `delta_partial` gives on packed copies of the same pieces. thetas and workers are read."""
+    lib = L.lib()
+    T, K = len(thetas), len(workers)
+    if K == 0:
+        raise L.EdtError("no workers")
+    if K > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"a piece-list partial takes at most {L.EDT_MAX_WORKERS} workers")
+    flat_w, numels, gdt, wdt = _check_list_operands(thetas, workers, None)
+    if T == 0:
+        if len(accs):
+            raise L.EdtError("accs: one tensor per piece")
+        return
+    dev = thetas[0].device
+    accs = _piece_columns("accs", [accs], numels, torch.float32, dev)
+    nbytes = lib.edt_delta_partial_list_workspace_bytes(T, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    numel = (ctypes.c_uint64 * T)(*numels)
+    L.check(lib.edt_delta_partial_list(_ptrs(thetas), L.dtype_code(gdt), _ptrs(flat_w), L.dtype_code(wdt), K,
+                                       int(k_total), _ptrs(accs), numel, T, L.ptr(ws), nbytes, L.stream_ptr(dev)),
+            "edt_delta_partial_list")
+
+
+def sgd_sum_list_to(thetas: list[torch.Tensor], parts: list[list[torch.Tensor]], momenta: list[torch.Tensor] | None,
+                    has_momentum: bool, lr: float, momentum_coef: float, nesterov: bool,
+                    outs: list[torch.Tensor]) -> None:
+    """`sgd_apply_sum` over T pieces in ONE launch, into `outs` (edt_sgd_sum_list_to): per piece
+    grad = -round(((parts[0][t] + parts[1][t]) + ...)) (fp32, that order), then the SGD update with
+    momenta[t] (theta's dtype, updated in place; required when momentum_coef != 0). thetas[t] is
+    only read: the new theta is stored to outs[t] (theta's dtype). outs[t] and the momentum equal
+    `sgd_apply_sum`'s theta and momentum on packed copies bit for bit."""
+    lib = L.lib()
+    T, N = len(thetas), len(parts)
+    if not 1 <= N <= L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"parts: 1 to {L.EDT_MAX_WORKERS} lists of fp32 partials")
+    if momentum_coef != 0 and momenta is None:
+        raise L.EdtError("momentum tensors are required when momentum != 0")
+    _, numels, gdt, _ = _check_list_operands(thetas, [thetas], momenta)
+    if T == 0:
+        if len(outs) or any(len(p) for p in parts):
+            raise L.EdtError("parts, outs: one tensor per piece")
+        return
+    dev = thetas[0].device
+    flat_p = _piece_columns("parts", parts, numels, torch.float32, dev)
+    outs = _piece_columns("outs", [outs], numels, gdt, dev)
+    nbytes = lib.edt_sgd_sum_list_to_workspace_bytes(T, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    numel = (ctypes.c_uint64 * T)(*numels)
+    m_arr = _ptrs(momenta) if momenta is not None else None
+    L.check(lib.edt_sgd_sum_list_to(_ptrs(thetas), L.dtype_code(gdt), _ptrs(flat_p), N, m_arr, int(has_momentum),
+                                    _ptrs(outs), numel, T, float(lr), float(momentum_coef), int(nesterov), L.ptr(ws),
+                                    nbytes, L.stream_ptr(dev)), "edt_sgd_sum_list_to")
+
+
+def theta_scatter_mix_list(thetas: list[torch.Tensor], srcs: list[torch.Tensor], live: list[list[torch.Tensor]],
+                           mix: float) -> None:
+    """The gathered new theta into theta's pieces and, merged, into the workers', ONE launch
+    (edt_theta_scatter_mix_list): thetas[t] <- srcs[t] (theta's dtype, a copy of the bits), and every
+    destination live[j][t] (nmix lists in one worker dtype, nmix from 0 to 64) becomes `lerp(mix,
+    live[j][t], srcs[t].to(worker dtype))` in the worker dtype bit for bit — `outer_step_list_mix`'s
+    merge. mix == 1.0 overwrites (the destination is not read). A mix outside (0, 1], or a piece of
+    theta or a destination overlapping any other operand, is refused: EdtError, nothing launched."""
+    lib = L.lib()
+    T = len(thetas)
+    live = [list(l) for l in live]
+    nmix = len(live)
+    if nmix > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"the merge takes at most {L.EDT_MAX_WORKERS} destinations")
+    mix = float(mix)
+    if not 0.0 < mix <= 1.0:                     # NaN fails both comparisons
+        raise L.EdtError(f"mix {mix} outside (0, 1]")
+    # the destinations stand where the workers do: one dtype, the pieces' sizes
+    flat_l, numels, gdt, wdt = _check_list_operands(thetas, live if nmix else [thetas], None)
+    if T == 0:
+        if len(srcs):
+            raise L.EdtError("srcs: one tensor per piece")
+        return
+    dev = thetas[0].device
+    srcs = _piece_columns("srcs", [srcs], numels, gdt, dev)
+    rs = sorted((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), w)
+                for ts, w in ((srcs, False), (thetas, True), (flat_l if nmix else [], True)) for t in ts if t.numel())
+    end_any = end_written = 0
+    for lo, hi, written in rs:
+        if lo < (end_any if written else end_written):
+            raise L.EdtError("a piece of theta or a merge destination overlaps another operand")
+        end_any = max(end_any, hi)
+        if written:
+            end_written = max(end_written, hi)
+    nbytes = lib.edt_theta_scatter_mix_list_workspace_bytes(T, nmix)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    numel = (ctypes.c_uint64 * T)(*numels)
+    L.check(lib.edt_theta_scatter_mix_list(_ptrs(thetas), L.dtype_code(gdt), _ptrs(srcs),
+                                           _ptrs(flat_l) if nmix else None, L.dtype_code(wdt if nmix else gdt), nmix,
+                                           mix, numel, T, L.ptr(ws), nbytes, L.stream_ptr(dev)),
+            "edt_theta_scatter_mix_list")
+
+
 def delta_partial(theta: torch.Tensor, workers: list[torch.Tensor], k_total: int,
                   acc: torch.Tensor, accumulate: bool = False) -> None:
     """acc (fp32) (+)= sum over the local workers of round((theta_k - theta) / k_total)."""

@@ -273,6 +273,53 @@ uint64_t edt_partial_sum_stats_doubles(int64_t nchunks);
 int edt_partial_sum_stats(const float* const* acc_f32, int nacc, int gdt, uint64_t n, const uint64_t* chunk_desc,
                           int64_t nchunks, double* out, void* stream);
 
+/* ---- the sharded fragment step's piece lists (Streaming DiLoCo across ranks) -----------------
+ * Fragment space is a fragment's runs laid back to back; a rank's shard of it cuts runs in the
+ * middle, so each phase of the sharded fragment step runs over a list of T PIECES: one contiguous
+ * stretch of numel[t] elements of every operand, given by one pointer per operand (a view into an
+ * arena, or into a compact fragment-space buffer). The three entries share edt_outer_step_list's
+ * conventions: host arrays of device pointers, numel[t] == 0 allowed (such a piece's pointers are
+ * not read), a device workspace (8-byte aligned, >= the entry's _workspace_bytes) that receives
+ * the table by a stream-ordered copy and must not be reused before the launch has run, one launch
+ * whatever T. A piece whose pointers are all 16-byte aligned takes vector accesses, any other
+ * scalar ones; every result is element-wise, so the bits depend neither on alignment nor on how
+ * the pieces are cut. T >= 0 (T == 0: nothing to do). Additive to ABI 6.
+ *
+ * edt_delta_partial_list — phase 1, edt_delta_partial over pieces, bit for bit:
+ *   acc_t[t][i] = sum_{k < K_local} round_g(round_g(f32(theta_k[k * T + t][i]) - f32(theta_t[t][i])) / K_total)
+ * the sum in fp32, local workers in order; true division unless K_total is a power of two. theta_t
+ * and theta_k are read, acc_t (fp32) is written. 1 <= K_local <= EDT_MAX_WORKERS, K_total >= 1.
+ *
+ * edt_sgd_sum_list_to — phase 2 on the owned shard's pieces, edt_sgd_apply_sum's sum and update:
+ *   a = round_g(((p_0 + p_1) + ...) + p_{nacc-1}),  p_r = parts[r * T + t]  (fp32, rank order)
+ *   grad = -a, then the torch.optim.SGD update with momentum_t[t] (updated in place; the table may
+ *   be null when momentum_coef == 0).
+ * theta_t is ONLY READ: the new theta (theta's dtype) is stored to out_t[t], as edt_sgd_delta_sum_q
+ * leaves theta alone. 1 <= nacc <= EDT_MAX_WORKERS.
+ *
+ * edt_theta_scatter_mix_list — phase 3 on every rank, over a whole bucket's pieces:
+ *   theta_t[t][i] = src_t[t][i]                      (theta's dtype, the bits as they are)
+ *   v = round_w(src);  live[j * T + t][i] = round_w(round_w(c0 * live) + round_w(c1 * v)),  j < nmix
+ * with c0 = (float)(1.0 - mix), c1 = (float)mix: edt_outer_step_list_mix's merge, i.e.
+ * edt_lerp(live, v, wdt, live, wdt, wdt, n, mix). mix == 1.0 stores v without reading the
+ * destination. mix must be finite and in (0, 1], 0 <= nmix <= EDT_MAX_WORKERS (0: theta only; live
+ * may then be null), else EDT_ERR_ARG. Stores follow the EDT_NT_STORES policy. Aliasing: theta's
+ * pieces and the destinations are written, so none of them may overlap src, theta, or another
+ * destination: EDT_ERR_ARG, nothing launched. */
+uint64_t edt_delta_partial_list_workspace_bytes(int T, int K_local);
+int edt_delta_partial_list(const void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K_local,
+                           int K_total, float* const* acc_t, const uint64_t* numel, int T, void* workspace,
+                           uint64_t workspace_bytes, void* stream);
+uint64_t edt_sgd_sum_list_to_workspace_bytes(int T, int nacc);
+int edt_sgd_sum_list_to(const void* const* theta_t, int gdt, const float* const* parts, int nacc,
+                        void* const* momentum_t, int has_momentum, void* const* out_t, const uint64_t* numel, int T,
+                        double lr, double momentum_coef, int nesterov, void* workspace, uint64_t workspace_bytes,
+                        void* stream);
+uint64_t edt_theta_scatter_mix_list_workspace_bytes(int T, int nmix);
+int edt_theta_scatter_mix_list(void* const* theta_t, int gdt, const void* const* src_t, void* const* live, int wdt,
+                               int nmix, double mix, const uint64_t* numel, int T, void* workspace,
+                               uint64_t workspace_bytes, void* stream);
+
 /* ---- block-quantized partial exchange (the sharded step's opt-in "reduce_q" schedule) --------
  * The reference moves checkpoints over a shared disk (EDT_LM/diloco.py:231-235, 302-308) and has
  * no wire format; reduce_ordered ships each rank's pseudo-gradient partial as fp32. These entries
