@@ -70,6 +70,12 @@ SIGNATURES = [
     ("edt_theta_scatter_mix_list_workspace_bytes", _U64, [_I, _I]),
     ("edt_theta_scatter_mix_list", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), ctypes.POINTER(_P), _I, _I, _D,
                                         ctypes.POINTER(_U64), _I, _P, _U64, _P]),
+    ("edt_delta_partial_q_frag_workspace_bytes", _U64, [_I, _I]),
+    ("edt_delta_partial_q_frag", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, _I, _I, ctypes.POINTER(_U64),
+                                      ctypes.POINTER(_U64), _I, _U64, _U64, _U64, _I, _P, _P, _P, _U64, _P]),
+    ("edt_sgd_sum_q_frag_to_workspace_bytes", _U64, [_I]),
+    ("edt_sgd_sum_q_frag_to", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_U64), ctypes.POINTER(_U64), _I, _U64, _U64,
+                                   ctypes.POINTER(_P), _I, _I, _P, _I, _P, _D, _D, _I, _P, _U64, _P]),
     ("edt_partial_sum_stats_doubles", _U64, [ctypes.c_int64]),
     ("edt_partial_sum_stats", _I, [ctypes.POINTER(_P), _I, _I, _U64, _P, ctypes.c_int64, _P, _P]),
     ("edt_q_region_bytes", _U64, [_U64, _I]),

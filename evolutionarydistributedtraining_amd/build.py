@@ -16,10 +16,12 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
-# one shared object from seven translation units (DiLoCo, pair merge + lerp, SLERP, ABI misc, the
-# quantized partial exchange, the pseudo-gradient statistics, the sharded fragment step's piece lists)
+# one shared object from eight translation units (DiLoCo, pair merge + lerp, SLERP, ABI misc, the
+# quantized partial exchange, the pseudo-gradient statistics, the sharded fragment step's piece lists
+# and its quantized phases)
 SOURCES = [os.path.join(CSRC, f) for f in ("edt_outer.hip", "edt_merge.hip", "edt_slerp.hip", "edt_abi.hip",
-                                           "edt_quant.hip", "edt_stats.hip", "edt_fragment.hip")]
+                                           "edt_quant.hip", "edt_stats.hip", "edt_fragment.hip",
+                                           "edt_fragment_q.hip")]
 HEADER = os.path.join(ROOT, "include", "edt_sync.h")
 DEPS = SOURCES + [HEADER, os.path.join(CSRC, "edt_common.h"), os.path.join(CSRC, "edt_step.h"),
                   os.path.join(CSRC, "edt_chunksum.h"), os.path.join(CSRC, "edt_mx.h")]

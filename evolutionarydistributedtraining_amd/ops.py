@@ -700,6 +700,104 @@ def _sgd_apply_sum_q(entry: str, theta, regions, fmt, momentum, has_momentum, lr
                                 int(nesterov), *grad_scale, L.stream_ptr(theta.device)), entry)
 
 
+# The sharded fragment step's quantized phases (sharded_fragments.py with wire_format=): one
+# fragment-space range [lo, lo + n), its arena operands as pieces (thetas[t], workers[k][t]: views of
+# the same sizes at any element offset; starts[t]: where piece t begins in fragment space), its
+# compact operands indexed by the offset in the range. What no piece covers is padding: +0.
+
+def _check_frag_pieces(starts, numels, lo: int, n: int) -> None:
+    if len(starts) != len(numels):
+        raise L.EdtError("starts: one fragment-space start per piece")
+    if lo < 0 or lo % 512:
+        raise L.EdtError(f"range start {lo} is not a non-negative multiple of 512")
+    end = lo
+    for t, (s, m) in enumerate(zip(starts, numels)):
+        if s < end:
+            raise L.EdtError(f"piece {t} starts before the range or before the end of the piece ahead of it: "
+                             "sorted, disjoint pieces")
+        end = s + m
+    if end > lo + n:
+        raise L.EdtError("the pieces leave the range")
+
+
+def delta_partial_q_frag(thetas: list[torch.Tensor], workers: list[list[torch.Tensor]], k_total: int, starts: list[int],
+                         lo: int, packed: torch.Tensor, region_elems: int, fmt,
+                         residual: torch.Tensor | None = None) -> None:
+    """`delta_partial_list`'s fp32 partial of the fragment-space range [lo, lo + n), n = the elements
+    `packed` holds, block-quantized into `packed` (uint8, n / region_elems regions back to back) in ONE
+    launch (edt_delta_partial_q_frag); the fp32 partial never reaches HBM. thetas[t] / workers[k][t]:
+    the T pieces covering the range (sorted, disjoint; views into the arenas, or for the workers
+    into fragment-space snapshots), starts[t] their fragment-space starts; what they do not cover is
+    padding and contributes +0. residual (fp32, n elements, the range's slice of the fragment's
+    residual): error feedback, `delta_partial_q`'s rule. The bytes are `delta_partial_q`'s on packed,
+    zero-padded copies, whatever the pieces' cut and alignment."""
+    lib = L.lib()
+    T, K = len(thetas), len(workers)
+    if K == 0:
+        raise L.EdtError("no workers")
+    if K > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"a fragment partial takes at most {L.EDT_MAX_WORKERS} workers")
+    code = _qfmt(fmt)
+    dev = L.require_device(packed, residual)
+    if region_elems <= 0 or region_elems % 512:
+        raise L.EdtError(f"region_elems {region_elems} is not a positive multiple of 512")
+    rb = q_region_bytes(region_elems, fmt)
+    if packed.dtype != torch.uint8 or packed.numel() % rb:
+        raise L.EdtError("packed: a uint8 buffer of whole regions of q_region_bytes each")
+    n = packed.numel() // rb * region_elems
+    _check_residual(residual, n)
+    flat_w, numels, gdt, wdt = _check_list_operands(thetas, workers, None)
+    if T and thetas[0].device != dev:
+        raise L.EdtError("operands on different devices")
+    starts = [int(s) for s in starts]
+    _check_frag_pieces(starts, numels, int(lo), n)
+    if T == 0:                       # a range that is all padding: the dtypes do not matter
+        gdt = wdt = torch.float32
+    nbytes = lib.edt_delta_partial_q_frag_workspace_bytes(T, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    u64 = ctypes.c_uint64 * max(1, T)
+    L.check(lib.edt_delta_partial_q_frag(_ptrs(thetas), L.dtype_code(gdt), _ptrs(flat_w), L.dtype_code(wdt), K,
+                                         int(k_total), u64(*starts), u64(*numels), T, int(lo), n, int(region_elems),
+                                         code, L.ptr(residual), L.ptr(packed), L.ptr(ws), nbytes, L.stream_ptr(dev)),
+            "edt_delta_partial_q_frag")
+
+
+def sgd_sum_q_frag_to(thetas: list[torch.Tensor], starts: list[int], lo: int, regions: list[torch.Tensor], fmt,
+                      momentum: torch.Tensor | None, has_momentum: bool, lr: float, momentum_coef: float,
+                      nesterov: bool, out: torch.Tensor) -> None:
+    """`sgd_apply_sum_q` on the owned shard [lo, lo + n) of fragment space, n = out.numel(), in ONE
+    launch, into `out` (edt_sgd_sum_q_frag_to): each of `regions` (uint8, q_region_bytes(n)) is
+    dequantized, they are summed in list order in fp32, then the SGD step. thetas[t]: theta's pieces
+    of the shard (only read), starts[t] their fragment-space starts. momentum (theta's dtype, n
+    elements, compact; required when momentum_coef != 0) is updated in place where a piece covers the
+    element; out (theta's dtype, compact) receives the new theta, and zero where none does. Out and
+    the momentum equal `sgd_apply_sum_q`'s theta and momentum on a packed copy bit for bit."""
+    lib = L.lib()
+    T = len(thetas)
+    code = _qfmt(fmt)
+    dev = L.require_device(out, momentum, *regions)
+    n = out.numel()
+    gdt = out.dtype
+    _check_regions(regions, n, fmt)
+    if len(regions) > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"regions: at most {L.EDT_MAX_WORKERS}")
+    if momentum_coef != 0 and momentum is None:
+        raise L.EdtError("a momentum buffer is required when momentum != 0")
+    _check_momentum(momentum, out)
+    _, numels, tdt, _ = _check_list_operands(thetas, [thetas], None)
+    if T and (tdt != gdt or thetas[0].device != dev):
+        raise L.EdtError("out must have theta's dtype and device")
+    starts = [int(s) for s in starts]
+    _check_frag_pieces(starts, numels, int(lo), n)
+    nbytes = lib.edt_sgd_sum_q_frag_to_workspace_bytes(T)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    u64 = ctypes.c_uint64 * max(1, T)
+    L.check(lib.edt_sgd_sum_q_frag_to(_ptrs(thetas), L.dtype_code(gdt), u64(*starts), u64(*numels), T, int(lo), n,
+                                      L.ptr_array(regions), len(regions), code, L.ptr(momentum), int(has_momentum),
+                                      L.ptr(out), float(lr), float(momentum_coef), int(nesterov), L.ptr(ws), nbytes,
+                                      L.stream_ptr(dev)), "edt_sgd_sum_q_frag_to")
+
+
 def partial_sum_stats_q(regions: list[torch.Tensor], fmt, gdt_like, plan: "SlerpPlan") -> torch.Tensor:
     """`partial_sum_stats` of the mean `sgd_apply_sum_q(theta, regions, fmt, ...)` (or
     `sgd_delta_sum_q`) would apply, read only (edt_partial_sum_stats_q): float64 [plan.nchunks, 2] on

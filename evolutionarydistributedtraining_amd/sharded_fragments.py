@@ -30,9 +30,29 @@ Per rank: a full theta replica, K_local worker arenas (unpadded), and per fragme
 momentum in fragment space (F_pad / N elements; the pad elements are never written). Nothing outside
 fragment p is read or written by its step.
 
+Quantized exchange (wire_format="mxfp8" | "mxfp4": Streaming DiLoCo's low-precision outer gradients).
+The partial crosses the links as OCP MX regions (ShardedOuterSync's reduce_q wire format, DESIGN §3:
+1.03 / 0.53 B per element instead of 4) with error feedback:
+
+  The unit of fragment space is world * 512 instead of world * 64, so every rank's region of every
+  bucket is whole 512-element waves; F_pad, the buckets and the momentum shards follow from it.
+  `send` / `recv` are uint8: a bucket [b, e) holds `world` regions of (e - b) / world elements,
+  [dest rank][payload | scales], at byte b * (bits / 8 + 1 / 32).
+  phase 1  per bucket: edt_delta_partial_q_frag over the bucket's pieces — the same fp32 partial,
+           gathered through the piece table in fragment space, + residual[p], quantized in registers
+           (the fp32 partial never reaches HBM), the new residual stored — then the all-to-all of
+           the packed bytes. All buckets before the first wait, as above.
+  phase 2  edt_sgd_sum_q_frag_to over the owned shard: the N received regions dequantized and
+           summed in rank order, the same SGD update; the new theta into the gather buffer (zero on
+           the padding). The all-gather of theta in theta's dtype and phase 3 are unchanged.
+  residual[p] (error_feedback=True): F_pad fp32 elements per fragment on this rank, in fragment
+  space, zero at the start; what the quantization of this rank's partial lost and adds back at the
+  fragment's next step. It is NOT checkpointed, by ShardedOuterSync.residual's rule: a restart
+  loses at most one step's quantization error per fragment.
+
 Not here, and not planned by this module: guard= (the statistics, screening and clip of
-ShardedOuterSync), quantized partials or a quantized gather, cpu_tails, the exact and reduce
-schedules, the C schedules of edt_comm.cpp, and bucket sizes tuned for xGMI.
+ShardedOuterSync), a quantized gather of theta' for fragments, stochastic rounding, cpu_tails, the
+exact and reduce schedules, the C schedules of edt_comm.cpp, and bucket sizes tuned for xGMI.
 """
 from __future__ import annotations
 
@@ -49,19 +69,27 @@ from .params import ParamArena, ParamLayout
 from .tracing import traced
 
 KERNEL_NAMES = ("delta_partial_list", "sgd_sum_list_to", "theta_scatter_mix_list")
+# with a wire format, phases 1 and 2 are these two instead; phase 3 stays theta_scatter_mix_list
+Q_KERNEL_NAMES = ("delta_partial_q_frag", "sgd_sum_q_frag_to", "theta_scatter_mix_list")
+WIRE_BITS = {"mxfp8": 8, "mxfp4": 4}
 
 
 class ShardedFragmentSync:
     def __init__(self, layout: ParamLayout, plan: FragmentPlan, theta_dtype: torch.dtype, worker_dtype: torch.dtype,
                  k_local: int, device, lr: float = 0.7, momentum: float = 0.9, nesterov: bool = True,
-                 bucket_elems: int = 1 << 26, group=None, kernels=None, comm: Collectives | None = None):
+                 bucket_elems: int = 1 << 26, group=None, kernels=None, comm: Collectives | None = None,
+                 wire_format: str | None = None, error_feedback: bool = True):
         check_sgd_hparams(lr, momentum, nesterov)
         if plan.layout.numels != layout.numels:
             raise EdtError("the fragment plan does not match the layout")
+        if wire_format is not None and wire_format not in WIRE_BITS:
+            raise EdtError(f"unknown wire format {wire_format!r}: None, 'mxfp8' or 'mxfp4'")
+        self.wire_format = wire_format
         self.kernels = kernels or _ops
-        missing = [m for m in KERNEL_NAMES if not hasattr(self.kernels, m)]
+        names = KERNEL_NAMES if wire_format is None else Q_KERNEL_NAMES
+        missing = [m for m in names if not hasattr(self.kernels, m)]
         if missing:
-            raise EdtError(f"the sharded fragment step needs kernels that provide {list(KERNEL_NAMES)}; "
+            raise EdtError(f"the sharded fragment step needs kernels that provide {list(names)}; "
                            f"{getattr(self.kernels, '__name__', type(self.kernels).__name__)} lacks {missing}")
         # the communicator seam: torch.distributed (RCCL / gloo) by default, or N virtual ranks on
         # one device (collectives.VirtualWorld)
@@ -78,8 +106,9 @@ class ShardedFragmentSync:
         self.workers = [ParamArena(layout, worker_dtype, device, torch.zeros(layout.total, dtype=worker_dtype, device=device))
                         for _ in range(k_local)]
         # fragment space: buckets of multiples of world * 64 elements, so every shard starts on a
-        # 16-byte boundary of the compact buffers
-        unit = self.world * 64
+        # 16-byte boundary of the compact buffers; with a wire format world * 512, so every rank's
+        # region is whole 512-element waves of the quantizing kernels
+        unit = self.world * (64 if wire_format is None else 512)
         bucket = max(unit, bucket_elems // unit * unit)
         self.f_pad = [math.ceil(plan.numel(p) / unit) * unit for p in range(len(plan))]
         self.buckets = [[(b, min(b + bucket, fp)) for b in range(0, fp, bucket)] for fp in self.f_pad]
@@ -88,8 +117,18 @@ class ShardedFragmentSync:
         # compact exchange buffers in fragment space, sized for the largest fragment: a bucket [b, e)
         # of `send` is [dest rank][per], of `recv` and `gathered` [src rank][per]
         top = max(self.f_pad)
-        self.send = torch.zeros(top, dtype=torch.float32, device=device)
-        self.recv = torch.zeros(top, dtype=torch.float32, device=device)
+        if wire_format is None:
+            self.send = torch.zeros(top, dtype=torch.float32, device=device)
+            self.recv = torch.zeros(top, dtype=torch.float32, device=device)
+            self.residual = None
+        else:
+            # packed: a bucket's `world` regions back to back start at byte _qbytes(b)
+            self.send = torch.zeros(self._qbytes(top), dtype=torch.uint8, device=device)
+            self.recv = torch.zeros(self._qbytes(top), dtype=torch.uint8, device=device)
+            # error feedback: per fragment, this rank's quantization error in fragment space (the
+            # padding stays zero); not checkpointed (module docstring)
+            self.residual = ([torch.zeros(fp, dtype=torch.float32, device=device) for fp in self.f_pad]
+                             if error_feedback else None)
         self.gathered = torch.zeros(top, dtype=theta_dtype, device=device)
         # OuterState's per-fragment semantics: a fragment's first step takes buf = grad
         self.fragment_has_momentum = [False] * len(plan)
@@ -109,6 +148,12 @@ class ShardedFragmentSync:
             s0, s1 = self._shard(b, e)
             yield b, e, s0, s1, off
             off += s1 - s0
+
+    def _qbytes(self, elems: int) -> int:
+        """Packed bytes of `elems` elements (a multiple of 512) as whole regions: payload + one scale
+        byte per 32 — linear in the elements, so also the byte offset of fragment-space element
+        `elems` in `send` / `recv`."""
+        return elems * WIRE_BITS[self.wire_format] // 8 + elems // 32
 
     def _check_fragment(self, p: int) -> None:
         if not 0 <= p < len(self.plan):
@@ -160,20 +205,35 @@ class ShardedFragmentSync:
             """The pieces' views of `buf`: at their arena offsets, or at their fragment-space ones."""
             return [buf[a:a + n] if arena else buf[f:f + n] for a, f, n in pieces]
 
+        fmt = self.wire_format
         works = []
         for b, e in self.buckets[p]:                # phase 1: every bucket before the first wait
             pc = plan.pieces(p, b, e)
+            deltas = ([cut(w.flat, pc, True) for w in self.workers] if snapshots is None
+                      else [cut(s, pc, False) for s in snapshots])
+            if fmt is not None:
+                # a bucket that is all padding is still quantized: its regions are sent like any other
+                q0, q1 = self._qbytes(b), self._qbytes(e)
+                k.delta_partial_q_frag(cut(theta, pc, True), deltas, self.k_total, [f for _, f, _ in pc], b,
+                                       self.send[q0:q1], (e - b) // self.world, fmt,
+                                       None if self.residual is None else self.residual[p][b:e])
+                works.append(self.comm.all_to_all(self.recv[q0:q1], self.send[q0:q1], async_op=True))
+                continue
             if pc:
-                deltas = ([cut(w.flat, pc, True) for w in self.workers] if snapshots is None
-                          else [cut(s, pc, False) for s in snapshots])
                 k.delta_partial_list(cut(theta, pc, True), deltas, self.k_total, cut(self.send, pc, False))
             works.append(self.comm.all_to_all(self.recv[b:e], self.send[b:e], async_op=True))
         gathers = []
         for (b, e, s0, s1, moff), w in zip(self._owned(p), works):      # phase 2 on the owned shard
             w.wait()
             pc = plan.pieces(p, s0, s1)
-            if pc:
-                per = s1 - s0
+            per = s1 - s0
+            if fmt is not None:
+                q0, rb = self._qbytes(b), self._qbytes(per)
+                regions = [self.recv[q0 + r * rb:q0 + (r + 1) * rb] for r in range(self.world)]
+                k.sgd_sum_q_frag_to(cut(theta, pc, True), [f for _, f, _ in pc], s0, regions, fmt,
+                                    None if self.mom is None else self.mom[p][moff:moff + per], has, self.lr,
+                                    self.momentum, self.nesterov, self.gathered[s0:s1])
+            elif pc:
                 parts = [[self.recv[b + r * per + f - s0:b + r * per + f - s0 + n] for _, f, n in pc]
                          for r in range(self.world)]
                 moms = None if self.mom is None else [self.mom[p][moff + f - s0:moff + f - s0 + n] for _, f, n in pc]
@@ -198,9 +258,16 @@ class ShardedFragmentSync:
 
     def wire_bytes(self, p: int) -> int:
         """Bytes this rank sends per step of fragment p (all-to-all / all-gather lower bound):
-        (N - 1) / N * F_pad * (4 + b_g) — the fp32 partials out, theta's dtype back."""
+        (N - 1) / N * F_pad * (4 + b_g) — the fp32 partials out, theta's dtype back. With a wire
+        format the partial costs bits / 8 + 1 / 32 bytes per element instead of 4 (F_pad is then a
+        multiple of world * 512). Computed from byte counts, not measured on a multi-GPU node."""
         f = (self.world - 1) / self.world
-        return int(f * self.f_pad[p] * (4 + self.theta.flat.element_size()))
+        return int(f * self.f_pad[p] * (self._partial_bytes() + self.theta.flat.element_size()))
+
+    def _partial_bytes(self) -> float:
+        """Bytes per element of the partial as it is exchanged: 4 (fp32), or the payload plus one
+        scale byte per 32 elements."""
+        return 4 if self.wire_format is None else WIRE_BITS[self.wire_format] / 8 + 1 / 32
 
     def kernel_bytes(self, p: int, merge: bool = True, mix: float = 1.0) -> int:
         """Algorithmic HBM bytes of the three kernels of one step of fragment p on this rank, steady
@@ -215,13 +282,16 @@ class ShardedFragmentSync:
           phase 3  F * (b_g            the gathered theta read
                         + b_g          theta's pieces written
                         + K_local * b_w                 the workers' pieces written (merge)
-                        + K_local * b_w)                and read first (merge with mix < 1)"""
+                        + K_local * b_w)                and read first (merge with mix < 1)
+        With a wire format, q = bits / 8 + 1 / 32: phase 1 writes q instead of 4, plus 8 with error
+        feedback (the residual read and written); phase 2 reads N * q instead of N * 4."""
         F, O = self.plan.numel(p), self._owned_elems(p)
         bg, bw = self.theta.flat.element_size(), self.workers[0].flat.element_size()
-        p1 = F * (self.k_local * bw + bg + 4)
-        p2 = O * (self.world * 4 + 2 * bg + (2 * bg if self.momentum else 0))
+        q = self._partial_bytes()
+        p1 = F * (self.k_local * bw + bg + q + (8 if self.residual is not None else 0))
+        p2 = O * (self.world * q + 2 * bg + (2 * bg if self.momentum else 0))
         p3 = F * (2 * bg + (self.k_local * bw * (1 if mix == 1.0 else 2) if merge else 0))
-        return p1 + p2 + p3
+        return int(p1 + p2 + p3)
 
     # ---------------------------------------------------------------------------------------
     # checkpoint bridge (cold path)

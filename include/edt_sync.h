@@ -390,6 +390,50 @@ int edt_delta_partial_q_sr(const void* theta_g, int gdt, const void* const* thet
 int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
                         int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream);
 
+/* ---- the sharded fragment step's quantized phases (Streaming DiLoCo's low-precision outer gradients) ----
+ * edt_delta_partial_list / edt_sgd_sum_list_to with the partial crossing the links as MX regions (the
+ * wire format above, unchanged) instead of fp32. Both entries work on one FRAGMENT-SPACE RANGE
+ * [lo, lo + n) of one fragment (lo % 512 == 0) and take its arena operands through ONE PIECE TABLE:
+ * T pieces, sorted and disjoint, each inside the range; piece t covers the fragment-space elements
+ * [start[t], start[t] + numel[t]) and gives one device pointer per arena operand, to the piece's first
+ * element. numel[t] == 0 is allowed (its pointers are not read), T == 0 too. Elements of the range that
+ * no piece covers are the padding beyond the fragment's size: they read as +0 for theta and every
+ * worker, and nothing of theirs is stored to an arena or to the momentum. The compact operands
+ * (residual, packed, regions, momentum, out) are indexed by the element's offset in the range and must
+ * be 16-byte aligned. The table is uploaded into `workspace` (8-byte aligned, >= the entry's
+ * _workspace_bytes; may be null when that is 0) by a stream-ordered copy, as the _list entries do; one
+ * launch whatever T. A lane takes vector loads where its 8 elements lie inside one piece whose arena
+ * addresses for them are 16-byte aligned and gathers element by element otherwise; the results do not
+ * depend on which. Additive to ABI 6.
+ *
+ * edt_delta_partial_q_frag — phase 1: p = edt_delta_partial_list's fp32 partial of the range, bit for
+ * bit (local workers in order; true division unless K_total is a power of two; +0 on the padding),
+ * never written to HBM, then edt_delta_partial_q's rule: with residual (nullable, n floats) p' = p +
+ * residual is quantized and residual = p' - D(q) is stored; `packed` receives n / region_elems
+ * regions back to back ([dest rank][payload | scales]). theta_k[k * T + t] is worker k's pointer for
+ * piece t: into its live arena, or into a compact fragment-space snapshot (base + start[t]).
+ * EDT_ERR_ARG, nothing launched: an unknown fmt, region_elems % 512 != 0, n % region_elems != 0,
+ * lo % 512 != 0, K out of range, a null pointer of a non-empty piece, pieces unsorted, overlapping or
+ * outside the range, packed null, packed or residual off a 16-byte boundary, a missing workspace.
+ *
+ * edt_sgd_sum_q_frag_to — phase 2 on the owned shard [lo, lo + n) (n % 512 == 0): the nacc received
+ * regions of n elements each are dequantized and summed in rank order and the SGD update applied,
+ * exactly as edt_sgd_apply_sum_q does; theta_t is ONLY READ. momentum (theta's dtype, n elements,
+ * compact; may be null when momentum_coef == 0) is updated in place where a piece covers the element
+ * and left alone on the padding; out (theta's dtype, n elements, compact) receives the new theta, and
+ * ZERO on the padding. EDT_ERR_ARG as above, and for nacc out of range, a null region or out, a
+ * missing momentum buffer, or a compact buffer off a 16-byte boundary. */
+uint64_t edt_delta_partial_q_frag_workspace_bytes(int T, int K_local);
+int edt_delta_partial_q_frag(const void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K_local,
+                             int K_total, const uint64_t* start, const uint64_t* numel, int T, uint64_t lo, uint64_t n,
+                             uint64_t region_elems, int fmt, float* residual, void* packed, void* workspace,
+                             uint64_t workspace_bytes, void* stream);
+uint64_t edt_sgd_sum_q_frag_to_workspace_bytes(int T);
+int edt_sgd_sum_q_frag_to(const void* const* theta_t, int gdt, const uint64_t* start, const uint64_t* numel, int T,
+                          uint64_t lo, uint64_t n, const void* const* regions, int nacc, int fmt, void* momentum,
+                          int has_momentum, void* out, double lr, double momentum_coef, int nesterov, void* workspace,
+                          uint64_t workspace_bytes, void* stream);
+
 /* The quantized gather (reduce_q with gather_format): the all-gather of the new theta is replaced
  * by an all-gather of each owner's quantized update, same wire format, and every rank adds the same
  * dequantized update to its replica.
