@@ -26,6 +26,16 @@ EDT_ABI_VERSION = 6         # include/edt_sync.h: the revision these signatures 
 
 _DT = {torch.float32: EDT_F32, torch.bfloat16: EDT_BF16}
 
+Q_BITS = {"mxfp8": 8, "mxfp4": 4}       # element bits of the MX wire formats
+
+
+def q_packed_bytes(elems: int, fmt: str) -> int:
+    """Packed bytes of `elems` elements (a multiple of 512) in wire format `fmt`, what
+    edt_q_region_bytes gives: the payload, then one E8M0 scale byte per 32 elements. Linear in
+    elems, so also the byte offset of element `elems` in a buffer of whole regions; for 512
+    elements, 512 times the wire bytes per element. Needs no compiled library."""
+    return elems * Q_BITS[fmt] // 8 + elems // 32
+
 # (name, restype, argtypes) for every symbol declared in include/edt_sync.h
 _P = ctypes.c_void_p
 _U64 = ctypes.c_uint64

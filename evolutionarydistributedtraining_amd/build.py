@@ -24,7 +24,8 @@ SOURCES = [os.path.join(CSRC, f) for f in ("edt_outer.hip", "edt_merge.hip", "ed
                                            "edt_fragment_q.hip")]
 HEADER = os.path.join(ROOT, "include", "edt_sync.h")
 DEPS = SOURCES + [HEADER, os.path.join(CSRC, "edt_common.h"), os.path.join(CSRC, "edt_step.h"),
-                  os.path.join(CSRC, "edt_chunksum.h"), os.path.join(CSRC, "edt_mx.h")]
+                  os.path.join(CSRC, "edt_chunksum.h"), os.path.join(CSRC, "edt_mx.h"),
+                  os.path.join(CSRC, "edt_table.h")]
 OUT = os.path.join(PKG_DIR, "libedt_sync.so")
 
 ARCH = "gfx950"

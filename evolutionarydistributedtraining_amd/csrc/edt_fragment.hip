@@ -15,18 +15,11 @@
 // is element-wise, so it does not depend on how the pieces are cut. The arithmetic is edt_step.h's
 // (add_delta, sgd_from_sum) and edt_common.h's (lerp_held).
 #include "edt_step.h"
-
-#include <algorithm>
+#include "edt_table.h"
 
 namespace {
 
-// outer_list_kernel's chunking (edt_outer.hip): the same rule, the same constants
-#ifndef EDT_LIST_ITERS
-#define EDT_LIST_ITERS 2
-#endif
-constexpr uint64_t kListChunk = (uint64_t)kBlock * kVec * EDT_LIST_ITERS;   // 4096 elements
-constexpr uint64_t kVecFlag = 1ull << 63;                                  // numel[t] bit: vector body ok
-constexpr uint64_t kListLdsMaxPieces = 8191;                               // (T + 1) x 8 B <= 64 KiB of LDS
+using namespace edt_table;      // kListChunk, kVecFlag: outer_list_kernel's chunking, the same constants
 
 // The device table of a launch, 8-byte words: prefix[T + 1] | numel[T] | the kernel's pointer columns,
 // each rows x T words, row-major (cols + (first row of the column + r) * T + t).
@@ -227,83 +220,12 @@ __global__ __launch_bounds__(kBlock) void theta_scatter_mix_list_kernel(PieceLis
 }
 
 // ---------------------------------------------------------------------------------------
-// host side: the table and the checks the three entries share
+// host side: the table is edt_table.h's chunk-prefix layout; what else the three entries share
 
-// One pointer column of an entry: rows x T host pointers, row-major; p == nullptr: an operand the
-// call does not use (zeros in the table, not read by the kernel).
-struct Column {
-    const void* const* p;
-    int rows;
-    const char* name;
-};
-
-uint64_t table_words(int T, int rows) { return (uint64_t)(2 + rows) * (uint64_t)T + 1; }
-
-// Fills h (table_words(T, all rows) words) from numel and the columns: every pointer of a non-empty
-// piece checked non-null ("<name>[t] is null", "<name>[r][t] is null" for a column of several rows),
-// the piece's vector flag from their 16-byte alignment, the chunk prefix sums. chunks = prefix[T].
-int fill_pieces(std::vector<uint64_t>& h, const uint64_t* numel, int T, const Column* cols, int ncols, uint64_t& chunks) {
-    int rows = 0;
-    for (int c = 0; c < ncols; ++c) rows += cols[c].rows;
-    h.assign(table_words(T, rows), 0);
-    uint64_t* prefix = h.data();
-    uint64_t* nflag = prefix + T + 1;
-    uint64_t* out = nflag + T;
-    for (int t = 0; t < T; ++t) {
-        const uint64_t n = numel[t];
-        if (n >= kVecFlag) return fail(EDT_ERR_ARG, "piece %d too large", t);
-        bool vec = true;
-        uint64_t row = 0;
-        for (int c = 0; c < ncols; ++c) {
-            for (int r = 0; r < cols[c].rows; ++r, ++row) {
-                if (!cols[c].p) continue;
-                const void* p = cols[c].p[(uint64_t)r * T + t];
-                if (n && !p)
-                    return cols[c].rows > 1 ? fail(EDT_ERR_ARG, "%s[%d][%d] is null", cols[c].name, r, t)
-                                            : fail(EDT_ERR_ARG, "%s[%d] is null", cols[c].name, t);
-                vec = vec && aligned16(p);
-                out[row * T + t] = reinterpret_cast<uintptr_t>(p);
-            }
-        }
-        prefix[t + 1] = prefix[t] + (n + kListChunk - 1) / kListChunk;
-        nflag[t] = n | (vec ? kVecFlag : 0);
-    }
-    chunks = prefix[T];
-    if (chunks > 0x7fffffffull) return fail(EDT_ERR_ARG, "too many elements for one launch");
-    return EDT_OK;
-}
-
-int check_workspace(const void* workspace, uint64_t workspace_bytes, uint64_t need) {
-    if (!workspace || workspace_bytes < need)
-        return fail(EDT_ERR_ARG, "workspace of %llu bytes needed", (unsigned long long)need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(EDT_ERR_ARG, "workspace must be 8-byte aligned");
-    return EDT_OK;
-}
-
-// The table uploaded by a stream-ordered copy (pageable source, overwritten by this thread's next
-// call: the runtime has read it when hipMemcpyAsync returns, as edt_outer_step_list relies on) and
-// the launch's view of it.
-int upload_table(PieceList& L, const std::vector<uint64_t>& h, void* workspace, int T, uint64_t chunks, hipStream_t st) {
-    hipError_t e = hipMemcpyAsync(workspace, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "piece table upload failed: %s", hipGetErrorString(e));
+// The launch's view of the uploaded table (edt_table.h's chunk-prefix layout).
+PieceList piece_list(const void* workspace, int T, uint64_t chunks) {
     const uint64_t* d = static_cast<const uint64_t*>(workspace);
-    L.prefix = d;
-    L.numel = d + T + 1;
-    L.cols = d + 2 * (uint64_t)T + 1;
-    L.T = (uint64_t)T;
-    L.chunks = chunks;
-    return EDT_OK;
-}
-
-struct ListLaunch {
-    unsigned grid;
-    size_t shm;
-    bool lds;
-};
-ListLaunch list_launch(int T, uint64_t chunks) {
-    const bool lds = (uint64_t)T <= kListLdsMaxPieces;
-    return {chunks > kMaxBlocks ? (unsigned)kMaxBlocks : (unsigned)chunks, lds ? (size_t)(T + 1) * sizeof(uint64_t) : 0,
-            lds};
+    return {d, d + T + 1, d + 2 * (uint64_t)T + 1, (uint64_t)T, chunks};
 }
 
 int check_piece_count(int T) {
@@ -312,36 +234,20 @@ int check_piece_count(int T) {
 }
 
 // Phase 3's aliasing rule over its non-empty pieces: theta's pieces and the destinations are
-// written, src is read; a written range may overlap nothing. One sort of the byte ranges, then a
-// sweep (as edt_outer_step_list_mix's check).
+// written, src is read; a written range may overlap nothing.
 int check_scatter_ranges(const void* const* src_t, void* const* theta_t, int gdt, void* const* live, int wdt, int nmix,
                          const uint64_t* numel, int T) {
-    struct Range {
-        uintptr_t lo, hi;
-        int written;
-    };
     const uint64_t bg = gdt == EDT_BF16 ? 2 : 4, bw = wdt == EDT_BF16 ? 2 : 4;
-    thread_local std::vector<Range> rs;
-    rs.clear();
-    auto push = [&](const void* p, uint64_t bytes, int written) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-        rs.push_back({lo, lo + bytes, written});
-    };
+    thread_local Sweep sw;
+    sw.clear();
     for (int t = 0; t < T; ++t) {
         const uint64_t n = numel[t];
-        if (!n) continue;
-        push(src_t[t], n * bg, 0);
-        push(theta_t[t], n * bg, 1);
-        for (int j = 0; j < nmix; ++j) push(live[(uint64_t)j * T + t], n * bw, 1);
+        sw.push(src_t[t], n * bg, false);
+        sw.push(theta_t[t], n * bg, true);
+        for (int j = 0; j < nmix; ++j) sw.push(live[(uint64_t)j * T + t], n * bw, true);
     }
-    std::sort(rs.begin(), rs.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
-    uintptr_t end_any = 0, end_written = 0;      // furthest end so far: of any range, of a written one
-    for (const Range& r : rs) {
-        if (r.lo < (r.written ? end_any : end_written))
-            return fail(EDT_ERR_ARG, "a piece of theta or a merge destination overlaps another operand");
-        if (r.hi > end_any) end_any = r.hi;
-        if (r.written && r.hi > end_written) end_written = r.hi;
-    }
+    if (!sw.writes_disjoint())
+        return fail(EDT_ERR_ARG, "a piece of theta or a merge destination overlaps another operand");
     return EDT_OK;
 }
 
@@ -351,17 +257,17 @@ extern "C" {
 
 uint64_t edt_delta_partial_list_workspace_bytes(int T, int K_local) {
     if (T < 0 || K_local < 1) return 0;
-    return table_words(T, 2 + K_local) * sizeof(uint64_t);
+    return prefix_table_words(T, 2 + K_local) * sizeof(uint64_t);
 }
 
 uint64_t edt_sgd_sum_list_to_workspace_bytes(int T, int nacc) {
     if (T < 0 || nacc < 1) return 0;
-    return table_words(T, 3 + nacc) * sizeof(uint64_t);
+    return prefix_table_words(T, 3 + nacc) * sizeof(uint64_t);
 }
 
 uint64_t edt_theta_scatter_mix_list_workspace_bytes(int T, int nmix) {
     if (T < 0 || nmix < 0) return 0;
-    return table_words(T, 2 + nmix) * sizeof(uint64_t);
+    return prefix_table_words(T, 2 + nmix) * sizeof(uint64_t);
 }
 
 int edt_delta_partial_list(const void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K_local,
@@ -381,12 +287,12 @@ int edt_delta_partial_list(const void* const* theta_t, int gdt, const void* cons
                            {theta_k, K_local, "theta_k"}};
     thread_local std::vector<uint64_t> h;
     uint64_t chunks;
-    if (int rc = fill_pieces(h, numel, T, cols, 3, chunks)) return rc;
+    if (!fill_prefix_table(h, numel, T, cols, 3, "piece", chunks, last_error())) return EDT_ERR_ARG;
     if (chunks == 0) return EDT_OK;
-    PieceList L;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = upload_table(L, h, workspace, T, chunks, st)) return rc;
-    const ListLaunch ll = list_launch(T, chunks);
+    if (int rc = upload_table(h, workspace, st, "piece")) return rc;
+    const PieceList L = piece_list(workspace, T, chunks);
+    const ListLaunch ll = list_launch((uint64_t)T, chunks, (uint64_t)T + 1);
     const float kdiv = (float)K_total, kinv = 1.0f / (float)K_total;
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_kc_div<KC_FUSED>(K_local, !is_pow2(K_total), [&](auto KC, auto DIV) {
@@ -419,12 +325,12 @@ int edt_sgd_sum_list_to(const void* const* theta_t, int gdt, const float* const*
                            {reinterpret_cast<const void* const*>(parts), nacc, "parts"}};
     thread_local std::vector<uint64_t> h;
     uint64_t chunks;
-    if ((rc = fill_pieces(h, numel, T, cols, 4, chunks))) return rc;
+    if (!fill_prefix_table(h, numel, T, cols, 4, "piece", chunks, last_error())) return EDT_ERR_ARG;
     if (chunks == 0) return EDT_OK;
-    PieceList L;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = upload_table(L, h, workspace, T, chunks, st))) return rc;
-    const ListLaunch ll = list_launch(T, chunks);
+    if ((rc = upload_table(h, workspace, st, "piece"))) return rc;
+    const PieceList L = piece_list(workspace, T, chunks);
+    const ListLaunch ll = list_launch((uint64_t)T, chunks, (uint64_t)T + 1);
     return with_dtype(gdt, [&](auto G) {
         return with_bool(ll.lds, [&](auto LDS) {
             sgd_sum_list_to_kernel<decltype(G)::value, decltype(LDS)::value><<<ll.grid, kBlock, ll.shm, st>>>(L, nacc, s);
@@ -452,13 +358,13 @@ int edt_theta_scatter_mix_list(void* const* theta_t, int gdt, const void* const*
                            {reinterpret_cast<const void* const*>(live), nmix, "live"}};
     thread_local std::vector<uint64_t> h;
     uint64_t chunks;
-    if (int rc = fill_pieces(h, numel, T, cols, 3, chunks)) return rc;
+    if (!fill_prefix_table(h, numel, T, cols, 3, "piece", chunks, last_error())) return EDT_ERR_ARG;
     if (chunks == 0) return EDT_OK;
     if (int rc = check_scatter_ranges(src_t, theta_t, gdt, live, wdt, nmix, numel, T)) return rc;
-    PieceList L;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = upload_table(L, h, workspace, T, chunks, st)) return rc;
-    const ListLaunch ll = list_launch(T, chunks);
+    if (int rc = upload_table(h, workspace, st, "piece")) return rc;
+    const PieceList L = piece_list(workspace, T, chunks);
+    const ListLaunch ll = list_launch((uint64_t)T, chunks, (uint64_t)T + 1);
     const float c0 = (float)(1.0 - mix), c1 = (float)mix;      // as edt_lerp forms them
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_bool(mix == 1.0, [&](auto COPY) {

@@ -20,7 +20,7 @@
 // stored to an arena or to the momentum.
 //
 // Piece lookup: one search per wave, then a linear advance per lane. The piece ends (8 B each) are
-// staged in LDS (up to kListLdsMaxPieces, edt_fragment.hip's limit; longer tables are searched in
+// staged in LDS (up to kListLdsMaxPieces, edt_table.h's limit; longer tables are searched in
 // global memory); a wave binary-searches the first piece that ends beyond its first element — the
 // same addresses in every lane, so the LDS reads broadcast and the branches are uniform — and each
 // lane steps forward from there to the piece of its own first element. With real tensors (pieces
@@ -36,11 +36,11 @@
 // paths rejoin before quant_store's shuffles.
 #include "edt_mx.h"
 #include "edt_step.h"
+#include "edt_table.h"
 
 namespace {
 
-constexpr uint64_t kVecFlag = 1ull << 63;                // start[t] bit: the piece's pointers allow vector loads
-constexpr uint64_t kListLdsMaxPieces = 8191;             // edt_fragment.hip's: at most 64 KiB of LDS
+using namespace edt_table;      // kVecFlag: the start[t] bit of a piece whose pointers allow vector loads
 
 // The device table of a launch, 8-byte words: end[T] | start[T] | the pointer columns, rows x T,
 // row-major. end and start are relative to the range's first element; end is non-decreasing.
@@ -209,55 +209,12 @@ __global__ __launch_bounds__(kBlock) void sgd_sum_q_frag_to_kernel(FragTable L, 
 }
 
 // ---------------------------------------------------------------------------------------
-// host side: the table and the checks the two entries share
+// host side: the table is edt_table.h's range layout
 
-// One pointer column of an entry: rows x T host pointers, row-major, to elements of elem_bytes.
-struct FragColumn {
-    const void* const* p;
-    int rows;
-    uint64_t elem_bytes;
-    const char* name;
-};
-
-uint64_t frag_table_words(int T, int rows) { return (uint64_t)(2 + rows) * (uint64_t)T; }
-
-// Fills h from the pieces of the range [lo, lo + n): sorted, disjoint and inside it (empty pieces
-// anywhere in it), every pointer of a non-empty piece non-null; the pointers rebased by the piece's
-// start, the piece's vector flag from the rebased pointers' 16-byte alignment.
-int fill_frag_table(std::vector<uint64_t>& h, const uint64_t* start, const uint64_t* numel, int T, uint64_t lo,
-                    uint64_t n, const FragColumn* cols, int ncols) {
-    int rows = 0;
-    for (int c = 0; c < ncols; ++c) rows += cols[c].rows;
-    h.assign(frag_table_words(T, rows), 0);
-    uint64_t* end = h.data();
-    uint64_t* sflag = end + T;
-    uint64_t* out = sflag + T;
-    uint64_t prev = lo;                                  // where the piece before ends
-    for (int t = 0; t < T; ++t) {
-        const uint64_t s = start[t], m = numel[t];
-        if (s < prev)
-            return fail(EDT_ERR_ARG, "piece %d starts before the range or before the end of piece %d: sorted, disjoint pieces",
-                        t, t - 1);
-        if (s - lo > n || m > n - (s - lo)) return fail(EDT_ERR_ARG, "piece %d leaves the range", t);
-        bool vec = true;
-        uint64_t row = 0;
-        for (int c = 0; c < ncols; ++c) {
-            for (int r = 0; r < cols[c].rows; ++r, ++row) {
-                const void* p = cols[c].p[(uint64_t)r * T + t];
-                if (!m) continue;                        // an empty piece's pointers are not read
-                if (!p)
-                    return cols[c].rows > 1 ? fail(EDT_ERR_ARG, "%s[%d][%d] is null", cols[c].name, r, t)
-                                            : fail(EDT_ERR_ARG, "%s[%d] is null", cols[c].name, t);
-                const uint64_t base = reinterpret_cast<uintptr_t>(p) - (s - lo) * cols[c].elem_bytes;
-                vec = vec && (base & 15u) == 0;
-                out[row * T + t] = base;
-            }
-        }
-        prev = s + m;
-        end[t] = prev - lo;
-        sflag[t] = (s - lo) | (vec && m ? kVecFlag : 0);
-    }
-    return EDT_OK;
+// The launch's view of the uploaded table. T == 0 (a range that is all padding): no table.
+FragTable frag_table(const void* workspace, int T) {
+    const uint64_t* d = static_cast<const uint64_t*>(workspace);
+    return {d, d + T, d + 2 * (uint64_t)T, (uint64_t)T};
 }
 
 int check_range(uint64_t lo, uint64_t n) {
@@ -266,44 +223,18 @@ int check_range(uint64_t lo, uint64_t n) {
     return EDT_OK;
 }
 
-int check_frag_workspace(const void* workspace, uint64_t workspace_bytes, uint64_t need) {
-    if (!need) return EDT_OK;
-    if (!workspace || workspace_bytes < need)
-        return fail(EDT_ERR_ARG, "workspace of %llu bytes needed", (unsigned long long)need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(EDT_ERR_ARG, "workspace must be 8-byte aligned");
-    return EDT_OK;
-}
-
-// The table uploaded by a stream-ordered copy (pageable source, overwritten by this thread's next
-// call: the runtime has read it when hipMemcpyAsync returns, as the _list entries rely on) and the
-// launch's view of it. T == 0 (a range that is all padding): no table, nothing copied.
-int upload_frag_table(FragTable& L, const std::vector<uint64_t>& h, void* workspace, int T, hipStream_t st) {
-    if (T > 0) {
-        hipError_t e = hipMemcpyAsync(workspace, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "piece table upload failed: %s", hipGetErrorString(e));
-    }
-    const uint64_t* d = static_cast<const uint64_t*>(workspace);
-    L.end = d;
-    L.start = d + T;
-    L.cols = d + 2 * (uint64_t)T;
-    L.T = (uint64_t)T;
-    return EDT_OK;
-}
-
-bool ends_in_lds(int T) { return (uint64_t)T <= kListLdsMaxPieces; }
-
 }  // namespace
 
 extern "C" {
 
 uint64_t edt_delta_partial_q_frag_workspace_bytes(int T, int K_local) {
     if (T < 0 || K_local < 1) return 0;
-    return frag_table_words(T, 1 + K_local) * sizeof(uint64_t);
+    return range_table_words(T, 1 + K_local) * sizeof(uint64_t);
 }
 
 uint64_t edt_sgd_sum_q_frag_to_workspace_bytes(int T) {
     if (T < 0) return 0;
-    return frag_table_words(T, 1) * sizeof(uint64_t);
+    return range_table_words(T, 1) * sizeof(uint64_t);
 }
 
 int edt_delta_partial_q_frag(const void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K_local,
@@ -324,15 +255,15 @@ int edt_delta_partial_q_frag(const void* const* theta_t, int gdt, const void* co
     if (!packed) return fail(EDT_ERR_ARG, "packed is null");
     if (!aligned16(packed) || !aligned16(residual))
         return fail(EDT_ERR_ARG, "the quantized partial needs 16-byte aligned compact buffers (packed, residual)");
-    if (int rc = check_frag_workspace(workspace, workspace_bytes, edt_delta_partial_q_frag_workspace_bytes(T, K_local)))
+    if (int rc = check_workspace(workspace, workspace_bytes, edt_delta_partial_q_frag_workspace_bytes(T, K_local)))
         return rc;
     const uint64_t bg = gdt == EDT_BF16 ? 2 : 4, bw = wdt == EDT_BF16 ? 2 : 4;
-    const FragColumn cols[] = {{theta_t, 1, bg, "theta_t"}, {theta_k, K_local, bw, "theta_k"}};
+    const Column cols[] = {{theta_t, 1, "theta_t", bg}, {theta_k, K_local, "theta_k", bw}};
     thread_local std::vector<uint64_t> h;
-    if (int rc = fill_frag_table(h, start, numel, T, lo, n, cols, 2)) return rc;
-    FragTable L;
+    if (!fill_range_table(h, start, numel, T, lo, n, cols, 2, last_error())) return EDT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = upload_frag_table(L, h, workspace, T, st)) return rc;
+    if (int rc = upload_table(h, workspace, st, "piece")) return rc;
+    const FragTable L = frag_table(workspace, T);
     QFragPartial a;
     a.residual = residual;
     a.packed = static_cast<uint8_t*>(packed);
@@ -343,17 +274,15 @@ int edt_delta_partial_q_frag(const void* const* theta_t, int gdt, const void* co
     a.K = K_local;
     a.kdiv = (float)K_total;
     a.kinv = 1.0f / (float)K_total;
-    const unsigned g = grid_for(n, true);
-    const bool lds = ends_in_lds(T);
-    const size_t shm = lds ? (size_t)T * sizeof(uint64_t) : 0;
+    const ListLaunch ll = list_launch((uint64_t)T, grid_for(n, true), (uint64_t)T);
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_fmt(fmt, [&](auto F) {
             return with_kc_div<KC_QUANT>(K_local, !is_pow2(K_total), [&](auto KC, auto DIV) {
                 return with_bool(residual != nullptr, [&](auto EF) {
-                    return with_bool(lds, [&](auto LDS) {
+                    return with_bool(ll.lds, [&](auto LDS) {
                         delta_partial_q_frag_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value,
                                                     decltype(DIV)::value, decltype(F)::value, decltype(EF)::value,
-                                                    decltype(LDS)::value><<<g, kBlock, shm, st>>>(L, a);
+                                                    decltype(LDS)::value><<<ll.grid, kBlock, ll.shm, st>>>(L, a);
                         return check_launch("delta_partial_q_frag_kernel");
                     });
                 });
@@ -385,22 +314,20 @@ int edt_sgd_sum_q_frag_to(const void* const* theta_t, int gdt, const uint64_t* s
     if (int rc = fill_table(P.p, regions, nacc, "regions", al)) return rc;
     if (!al)
         return fail(EDT_ERR_ARG, "the quantized sum needs 16-byte aligned compact buffers (regions, momentum, out)");
-    if (int rc = check_frag_workspace(workspace, workspace_bytes, edt_sgd_sum_q_frag_to_workspace_bytes(T))) return rc;
-    const FragColumn cols[] = {{theta_t, 1, gdt == EDT_BF16 ? 2u : 4u, "theta_t"}};
+    if (int rc = check_workspace(workspace, workspace_bytes, edt_sgd_sum_q_frag_to_workspace_bytes(T))) return rc;
+    const Column cols[] = {{theta_t, 1, "theta_t", gdt == EDT_BF16 ? 2u : 4u}};
     thread_local std::vector<uint64_t> h;
-    if (int rc = fill_frag_table(h, start, numel, T, lo, n, cols, 1)) return rc;
-    FragTable L;
+    if (!fill_range_table(h, start, numel, T, lo, n, cols, 1, last_error())) return EDT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = upload_frag_table(L, h, workspace, T, st)) return rc;
-    const unsigned g = grid_for(n, true);
-    const bool lds = ends_in_lds(T);
-    const size_t shm = lds ? (size_t)T * sizeof(uint64_t) : 0;
+    if (int rc = upload_table(h, workspace, st, "piece")) return rc;
+    const FragTable L = frag_table(workspace, T);
+    const ListLaunch ll = list_launch((uint64_t)T, grid_for(n, true), (uint64_t)T);
     void* mom = s.use_momentum ? momentum : nullptr;
     return with_dtype(gdt, [&](auto G) {
         return with_fmt(fmt, [&](auto F) {
-            return with_bool(lds, [&](auto LDS) {
+            return with_bool(ll.lds, [&](auto LDS) {
                 sgd_sum_q_frag_to_kernel<decltype(G)::value, decltype(F)::value, decltype(LDS)::value>
-                    <<<g, kBlock, shm, st>>>(L, P, nacc, mom, out, n, s);
+                    <<<ll.grid, kBlock, ll.shm, st>>>(L, P, nacc, mom, out, n, s);
                 return check_launch("sgd_sum_q_frag_to_kernel");
             });
         });

@@ -2,11 +2,13 @@
 // arenas or tensor lists, its sharded halves (partial sums, SGD on a shard) and the stream-ceiling
 // probe, with their C ABI entries (include/edt_sync.h).
 #include "edt_step.h"
+#include "edt_table.h"
 
-#include <algorithm>
 #include <atomic>
 
 namespace {
+
+using namespace edt_table;      // the list steps' host side, and kListChunk and kVecFlag for their kernels
 
 // ---------------------------------------------------------------------------------------
 // DiLoCo outer step
@@ -200,12 +202,7 @@ __global__ __launch_bounds__(kBlock, EDT_MIN_WAVES) void outer_kernel(OuterArgs 
 // chunk b to a workgroup, which finds its tensor t by a binary search over the chunk prefix
 // sums (uniform across the workgroup) and runs the same per-thread 8-element body as
 // outer_kernel on it. Tensors whose operands are not all 16-byte aligned take the scalar body.
-#ifndef EDT_LIST_ITERS          // 8-element iterations per thread per chunk
-#define EDT_LIST_ITERS 2        // measured: 2-4 with the grid-stride loop beat 1 and 8-64
-#endif
-constexpr uint64_t kListChunk = (uint64_t)kBlock * kVec * EDT_LIST_ITERS;   // 4096 elements
-constexpr uint64_t kVecFlag = 1ull << 63;                          // numel[t] bit: vector body ok
-
+// (kListChunk, kVecFlag and the table's host side: edt_table.h.)
 struct ListArgs {
     const uint64_t* prefix;     // T + 1 chunk prefix sums
     const uint64_t* numel;      // T, kVecFlag | numel
@@ -468,17 +465,14 @@ int launch_outer(int gdt, int wdt, const OuterArgs& a, bool vec, hipStream_t s) 
     });
 }
 
-constexpr uint64_t kListLdsMaxTensors = 8191;          // (T + 1) x 8 B <= 64 KiB of LDS
-
 template <bool SC, class LA>
-int launch_list(int gdt, int wdt, const LA& L, bool div_exact, unsigned grid, hipStream_t s) {
-    const bool lds = L.T <= kListLdsMaxTensors;
-    const size_t shm = lds ? (size_t)(L.T + 1) * sizeof(uint64_t) : 0;
+int launch_list(int gdt, int wdt, const LA& L, bool div_exact, hipStream_t s) {
+    const ListLaunch ll = list_launch(L.T, L.chunks, L.T + 1);      // grid-stride over chunks, the prefix sums in LDS
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_kc_div<KC_FUSED>(L.K, div_exact, [&](auto KC, auto DIV) {
-            return with_bool(lds, [&](auto LDS) {
+            return with_bool(ll.lds, [&](auto LDS) {
                 outer_list_kernel<decltype(G)::value, decltype(W)::value, decltype(KC)::value, decltype(DIV)::value,
-                                  decltype(LDS)::value, SC><<<grid, kBlock, shm, s>>>(L);
+                                  decltype(LDS)::value, SC><<<ll.grid, kBlock, ll.shm, s>>>(L);
                 return check_launch("outer_list_kernel");
             });
         });
@@ -486,18 +480,17 @@ int launch_list(int gdt, int wdt, const LA& L, bool div_exact, unsigned grid, hi
 }
 
 // The mixing list step: mx is MX_BLEND, MX_HELD (the host has checked KC > 0 for it) or MX_COPY.
-int launch_list_mix(int gdt, int wdt, const ListArgsMix& L, bool div_exact, int mx, unsigned grid, hipStream_t s) {
-    const bool lds = L.T <= kListLdsMaxTensors;
-    const size_t shm = lds ? (size_t)(L.T + 1) * sizeof(uint64_t) : 0;
+int launch_list_mix(int gdt, int wdt, const ListArgsMix& L, bool div_exact, int mx, hipStream_t s) {
+    const ListLaunch ll = list_launch(L.T, L.chunks, L.T + 1);
     return with_pair(gdt, wdt, [&](auto G, auto W) {
         return with_kc_div<KC_FUSED>(L.K, div_exact, [&](auto KC, auto DIV) {
-            return with_bool(lds, [&](auto LDS) {
+            return with_bool(ll.lds, [&](auto LDS) {
                 constexpr int GD = decltype(G)::value, WD = decltype(W)::value, KCV = decltype(KC)::value,
                               DV = decltype(DIV)::value;
                 constexpr bool LD = decltype(LDS)::value;
-                if (mx == MX_COPY) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_COPY><<<grid, kBlock, shm, s>>>(L);
-                else if (mx == MX_BLEND) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_BLEND><<<grid, kBlock, shm, s>>>(L);
-                else if constexpr (KCV > 0) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_HELD><<<grid, kBlock, shm, s>>>(L);
+                if (mx == MX_COPY) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_COPY><<<ll.grid, kBlock, ll.shm, s>>>(L);
+                else if (mx == MX_BLEND) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_BLEND><<<ll.grid, kBlock, ll.shm, s>>>(L);
+                else if constexpr (KCV > 0) outer_list_kernel<GD, WD, KCV, DV, LD, false, MX_HELD><<<ll.grid, kBlock, ll.shm, s>>>(L);
                 else return fail(EDT_ERR_ARG, "the held merge needs a compile-time worker count");
                 return check_launch("outer_list_kernel (mix)");
             });
@@ -710,7 +703,7 @@ int edt_outer_step_ws(void* theta_g, int gdt, const void* const* theta_k, int wd
 
 uint64_t edt_outer_list_workspace_bytes(int T, int K) {
     if (T < 0 || K < 1) return 0;
-    return (uint64_t)(5 * (uint64_t)T + 1 + (uint64_t)K * T) * sizeof(uint64_t);
+    return prefix_table_words(T, 3 + (uint64_t)K) * sizeof(uint64_t);     // theta | mom | w[K] | tail_off
 }
 
 uint64_t edt_outer_list_mix_workspace_bytes(int T, int K, int nmix) {
@@ -730,43 +723,29 @@ struct MixSpec {
 // The aliasing rule of the mixing step over its non-empty runs: live[j][r] may be exactly
 // theta_k[j][r] (same pointer, hence the same elements in the same thread); any other overlap of a
 // destination with theta, the momentum, a worker or another destination is refused. `held` is set
-// when every destination is its worker and nmix == K. One sort of the byte ranges, then a sweep.
+// when every destination is its worker and nmix == K.
 static int check_mix_ranges(void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
                             void* const* momentum_t, bool use_momentum, const uint64_t* numel, int T,
                             const MixSpec& mx, bool& held) {
-    struct Range {
-        uintptr_t lo, hi;
-        int live;            // a destination (written in the worker dtype)
-    };
     const uint64_t bg = gdt == EDT_BF16 ? 2 : 4, bw = wdt == EDT_BF16 ? 2 : 4;
-    thread_local std::vector<Range> rs;
-    rs.clear();
+    thread_local Sweep sw;
+    sw.clear();
     held = mx.nmix == K;
-    auto push = [&](const void* p, uint64_t bytes, int live) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-        rs.push_back({lo, lo + bytes, live});
-    };
     for (int t = 0; t < T; ++t) {
         const uint64_t n = numel[t];
         if (!n) continue;
-        push(theta_t[t], n * bg, 0);
-        if (use_momentum) push(momentum_t[t], n * bg, 0);
-        for (int j = 0; j < mx.nmix; ++j) push(mx.live[(uint64_t)j * T + t], n * bw, 1);
+        sw.push(theta_t[t], n * bg, false);
+        if (use_momentum) sw.push(momentum_t[t], n * bg, false);
+        for (int j = 0; j < mx.nmix; ++j) sw.push(mx.live[(uint64_t)j * T + t], n * bw, true);
         for (int k = 0; k < K; ++k) {
             const void* w = theta_k[(uint64_t)k * T + t];
             if (k < mx.nmix && w == mx.live[(uint64_t)k * T + t]) continue;      // the allowed alias: one range
             held = false;
-            push(w, n * bw, 0);
+            sw.push(w, n * bw, false);
         }
     }
-    std::sort(rs.begin(), rs.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
-    uintptr_t end_any = 0, end_live = 0;      // furthest end so far: of any range, of a destination
-    for (const Range& r : rs) {
-        if (r.lo < (r.live ? end_any : end_live))
-            return fail(EDT_ERR_ARG, "a merge destination overlaps another operand (only live[j] == theta_k[j] may alias)");
-        if (r.hi > end_any) end_any = r.hi;
-        if (r.live && r.hi > end_live) end_live = r.hi;
-    }
+    if (!sw.writes_disjoint())
+        return fail(EDT_ERR_ARG, "a merge destination overlaps another operand (only live[j] == theta_k[j] may alias)");
     return EDT_OK;
 }
 
@@ -797,67 +776,24 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     if (sg.use_momentum && !momentum_t) return fail(EDT_ERR_ARG, "momentum table is null");
     if (mx && !mx->live) return fail(EDT_ERR_ARG, "live is null");
     const uint64_t need = mx ? edt_outer_list_mix_workspace_bytes(T, K, mx->nmix) : edt_outer_list_workspace_bytes(T, K);
-    if (!workspace || workspace_bytes < need)
-        return fail(EDT_ERR_ARG, "workspace of %llu bytes needed", (unsigned long long)need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(EDT_ERR_ARG, "workspace must be 8-byte aligned");
+    if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
     if (tail && (gdt != EDT_BF16 || !tail_off)) return fail(EDT_ERR_ARG, "tail bits need a bf16 master and byte offsets");
     // table: prefix[T+1] | numel[T] | theta[T] | mom[T] | w[K*T] | tail_off[T] | live[nmix*T] (mx)   (all 8-byte words)
+    const Column cols[] = {{theta_t, 1, "theta_t"},
+                           {sg.use_momentum ? momentum_t : nullptr, 1, "momentum_t"},
+                           {theta_k, K, "theta_k", 0, true},
+                           {nullptr, 1, "tail_off", 0, false, tail ? tail_off : nullptr},
+                           {mx ? mx->live : nullptr, mx ? mx->nmix : 0, "live", 0, true}};
     thread_local std::vector<uint64_t> h;
-    h.assign(need / sizeof(uint64_t), 0);
-    uint64_t* prefix = h.data();
-    uint64_t* nflag = prefix + T + 1;
-    uint64_t* pth = nflag + T;
-    uint64_t* pmo = pth + T;
-    uint64_t* pw = pmo + T;
-    uint64_t* ptail = pw + (uint64_t)K * T;
-    uint64_t* plive = ptail + T;
-    if (tail)
-        for (int t = 0; t < T; ++t) ptail[t] = tail_off[t];
-    for (int t = 0; t < T; ++t) {
-        const uint64_t n = numel[t];
-        if (n >= kVecFlag) return fail(EDT_ERR_ARG, "tensor %d too large", t);
-        bool vec = true;
-        if (n) {
-            if (!theta_t[t]) return fail(EDT_ERR_ARG, "theta_t[%d] is null", t);
-            vec = aligned16(theta_t[t]);
-            if (sg.use_momentum) {
-                if (!momentum_t[t]) return fail(EDT_ERR_ARG, "momentum_t[%d] is null", t);
-                vec = vec && aligned16(momentum_t[t]);
-            }
-            for (int k = 0; k < K; ++k) {
-                const void* p = theta_k[(uint64_t)k * T + t];
-                if (!p) return fail(EDT_ERR_ARG, "theta_k[%d][%d] is null", k, t);
-                vec = vec && aligned16(p);
-            }
-            if (mx)
-                for (int j = 0; j < mx->nmix; ++j) {
-                    const void* p = mx->live[(uint64_t)j * T + t];
-                    if (!p) return fail(EDT_ERR_ARG, "live[%d][%d] is null", j, t);
-                    vec = vec && aligned16(p);
-                }
-        }
-        prefix[t + 1] = prefix[t] + (n + kListChunk - 1) / kListChunk;
-        nflag[t] = n | (vec ? kVecFlag : 0);
-        pth[t] = reinterpret_cast<uintptr_t>(theta_t[t]);
-        pmo[t] = sg.use_momentum ? reinterpret_cast<uintptr_t>(momentum_t[t]) : 0;
-        for (int k = 0; k < K; ++k) pw[(uint64_t)k * T + t] = reinterpret_cast<uintptr_t>(theta_k[(uint64_t)k * T + t]);
-        if (mx)
-            for (int j = 0; j < mx->nmix; ++j)
-                plive[(uint64_t)j * T + t] = reinterpret_cast<uintptr_t>(mx->live[(uint64_t)j * T + t]);
-    }
-    const uint64_t chunks = prefix[T];
+    uint64_t chunks;
+    if (!fill_prefix_table(h, numel, T, cols, 5, "tensor", chunks, last_error())) return EDT_ERR_ARG;
     if (chunks == 0) return EDT_OK;
-    if (chunks > 0x7fffffffull) return fail(EDT_ERR_ARG, "too many elements for one launch");
     bool held = false;
     if (mx)
         if (int rc = check_mix_ranges(theta_t, gdt, theta_k, wdt, K, momentum_t, sg.use_momentum != 0, numel, T, *mx, held))
             return rc;
     hipStream_t st = (hipStream_t)stream;
-    // pageable source, overwritten by this thread's next call: the runtime has read it when
-    // hipMemcpyAsync returns and the copy is stream-ordered on the device — pinned by
-    // tests/test_gpu_list_step.py::test_back_to_back_steps (two tables of up to 4.5 MB, no host wait)
-    hipError_t e = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "tensor table upload failed: %s", hipGetErrorString(e));
+    if (int rc = upload_table(h, workspace, st, "tensor")) return rc;
     const uint64_t* d = static_cast<const uint64_t*>(workspace);
     std::conditional_t<SC, ListArgsScaled, ListArgsMix> L;      // the plain entries launch its ListArgs base
     if constexpr (SC) L.grad_scale = grad_scale;
@@ -874,7 +810,6 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
     L.sgd = sg;
     L.tail = tail;
     L.tail_off = d + 4 * (uint64_t)T + 1 + (uint64_t)K * T;
-    const unsigned grid = chunks > kMaxBlocks ? (unsigned)kMaxBlocks : (unsigned)chunks;   // grid-stride
     if constexpr (!SC) {
         if (mx) {
             L.live = reinterpret_cast<void* const*>(L.tail_off + T);
@@ -883,11 +818,11 @@ static int outer_step_list_impl(void* const* theta_t, int gdt, const void* const
             L.c1 = (float)mx->mix;
             const bool kc = K == 1 || K == 2 || K == 3 || K == 4 || K == 8;       // with_kc_div<KC_FUSED>'s bodies
             const int mode = mx->mix == 1.0 ? MX_COPY : held && kc ? MX_HELD : MX_BLEND;
-            return launch_list_mix(gdt, wdt, L, !is_pow2(K), mode, grid, st);
+            return launch_list_mix(gdt, wdt, L, !is_pow2(K), mode, st);
         }
-        return launch_list<SC>(gdt, wdt, static_cast<const ListArgs&>(L), !is_pow2(K), grid, st);
+        return launch_list<SC>(gdt, wdt, static_cast<const ListArgs&>(L), !is_pow2(K), st);
     } else {
-        return launch_list<SC>(gdt, wdt, L, !is_pow2(K), grid, st);
+        return launch_list<SC>(gdt, wdt, L, !is_pow2(K), st);
     }
 }
 

@@ -9,6 +9,7 @@
 #include "edt_chunksum.h"
 #include "edt_mx.h"
 #include "edt_step.h"
+#include "edt_table.h"
 
 namespace {
 
@@ -552,8 +553,8 @@ int edt_delta_stats(const void* theta_g, int gdt, const void* const* theta_k, in
 
 uint64_t edt_delta_stats_list_workspace_bytes(int T, int K) {
     if (T < 0 || K < 1 || K > EDT_MAX_WORKERS) return 0;
-    // table: theta[T] | w[K*T] | vec[T]   (all 8-byte words)
-    return ((uint64_t)K + 2) * (uint64_t)T * sizeof(uint64_t);
+    // table (edt_table.h's flag-column layout): theta[T] | w[K*T] | vec[T]
+    return edt_table::flag_table_words(T, 1 + (uint64_t)K) * sizeof(uint64_t);
 }
 
 int edt_delta_stats_list(const void* const* theta_t, int gdt, const void* const* theta_k, int wdt, int K,
@@ -569,36 +570,14 @@ int edt_delta_stats_list(const void* const* theta_t, int gdt, const void* const*
     if (!theta_t || !theta_k || !numel) return fail(EDT_ERR_ARG, "null tensor table");
     if (!chunk_desc || !out) return fail(EDT_ERR_ARG, "null chunk table or output");
     if (reinterpret_cast<uintptr_t>(out) & 7u) return fail(EDT_ERR_ARG, "out must be 8-byte aligned");
-    const uint64_t need = edt_delta_stats_list_workspace_bytes(T, K);
-    if (!workspace || workspace_bytes < need)
-        return fail(EDT_ERR_ARG, "workspace of %llu bytes needed", (unsigned long long)need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(EDT_ERR_ARG, "workspace must be 8-byte aligned");
+    using namespace edt_table;
+    if (int rc = check_workspace(workspace, workspace_bytes, edt_delta_stats_list_workspace_bytes(T, K))) return rc;
+    const Column cols[] = {{theta_t, 1, "theta_t"}, {theta_k, K, "theta_k", 0, true}};
     thread_local std::vector<uint64_t> h;
-    h.assign(need / sizeof(uint64_t), 0);
-    uint64_t* pth = h.data();
-    uint64_t* pw = pth + T;
-    uint64_t* pvec = pw + (uint64_t)K * T;
-    bool all_vec = true;
-    for (int t = 0; t < T; ++t) {
-        bool vec = true;
-        if (numel[t]) {                               // an empty tensor has no chunks: never read
-            if (!theta_t[t]) return fail(EDT_ERR_ARG, "theta_t[%d] is null", t);
-            vec = aligned16(theta_t[t]);
-            for (int k = 0; k < K; ++k) {
-                const void* p = theta_k[(uint64_t)k * T + t];
-                if (!p) return fail(EDT_ERR_ARG, "theta_k[%d][%d] is null", k, t);
-                vec = vec && aligned16(p);
-            }
-        }
-        pth[t] = reinterpret_cast<uintptr_t>(theta_t[t]);
-        for (int k = 0; k < K; ++k) pw[(uint64_t)k * T + t] = reinterpret_cast<uintptr_t>(theta_k[(uint64_t)k * T + t]);
-        pvec[t] = vec ? 1 : 0;
-        all_vec = all_vec && vec;
-    }
+    bool all_vec;
+    if (!fill_flag_table(h, numel, T, cols, 2, all_vec, last_error())) return EDT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    // pageable source, overwritten by this thread's next call: stream-ordered, as edt_outer_step_list's
-    hipError_t e = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return fail(EDT_ERR_LAUNCH, "tensor table upload failed: %s", hipGetErrorString(e));
+    if (int rc = upload_table(h, workspace, s, "tensor")) return rc;
     const uint64_t* d = static_cast<const uint64_t*>(workspace);
     StatsListArgs a;
     memset(&a, 0, sizeof(a));

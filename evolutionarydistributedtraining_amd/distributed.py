@@ -101,7 +101,7 @@ import numpy as np
 import torch
 
 from . import ops as _ops
-from ._lib import EdtError
+from ._lib import Q_BITS, EdtError, q_packed_bytes
 from .collectives import Collectives, TorchCollectives
 from .diloco import check_sgd_hparams
 from .guard import (NonFiniteWorkers, OuterGuard, fold_remeasured, guard_decision, report, sequential_total,
@@ -112,9 +112,6 @@ from .tracing import trange, traced
 
 def _timing_event():
     return torch.cuda.Event(enable_timing=True)
-
-
-_Q_BITS = {"mxfp8": 8, "mxfp4": 4}       # element bits of the reduce_q wire formats
 
 
 class _Verdict(NamedTuple):
@@ -171,12 +168,12 @@ class ShardedOuterSync:
             raise ValueError((mode, broadcast))
         if mode.startswith("reduce") and broadcast == "workers":
             raise ValueError("the reduce schedules need the full theta replica (broadcast='theta')")
-        if mode == "reduce_q" and wire_format not in _Q_BITS:
+        if mode == "reduce_q" and wire_format not in Q_BITS:
             raise ValueError(f"wire_format {wire_format!r}: 'mxfp8' or 'mxfp4'")
         if gather_format is not None:
             if mode != "reduce_q":
                 raise ValueError("gather_format quantizes the gather of mode='reduce_q' only")
-            if gather_format not in _Q_BITS:
+            if gather_format not in Q_BITS:
                 raise ValueError(f"gather_format {gather_format!r}: None, 'mxfp8' or 'mxfp4'")
         if rounding not in ("nearest", "stochastic"):
             raise ValueError(f"rounding {rounding!r}: 'nearest' or 'stochastic'")
@@ -200,7 +197,7 @@ class ShardedOuterSync:
         cands = {key: v for key, v in cands.items()
                  if mode in ("auto", key[0]) and broadcast in ("auto", key[1])}
         if mode == "reduce_q":                         # opt-in only: never a candidate of "auto"
-            cands = {("reduce_q", "theta"): _Q_BITS[wire_format] / 8 + 1 / 32 + gb}
+            cands = {("reduce_q", "theta"): q_packed_bytes(512, wire_format) / 512 + gb}
         # fewest wire bytes per element; ties go to the bit-exact schedule, then to the one whose
         # cross-rank sum has a fixed order (reduce_ordered) over RCCL's own (reduce)
         pref = {"exact": 0, "reduce_ordered": 1, "reduce": 2, "reduce_q": 3}
@@ -282,10 +279,9 @@ class ShardedOuterSync:
         return b + self.rank * per, b + (self.rank + 1) * per
 
     def _q_bytes(self, elems: int, fmt: str | None = None) -> int:
-        """Packed bytes of `elems` elements (a multiple of 512) in this sync's wire format (or in
-        `fmt`): the payload and one scale byte per 32 elements. Linear in elems, so it is also the
-        byte offset of element offset `elems` in the send / receive buffers."""
-        return elems * _Q_BITS[fmt or self.wire_format] // 8 + elems // 32
+        """q_packed_bytes in this sync's wire format (or in `fmt`): also the byte offset of element
+        offset `elems` in the send / receive buffers."""
+        return q_packed_bytes(elems, fmt or self.wire_format)
 
     def _launch(self, fn, *args, **kw):
         """A local kernel, bracketed by timing events on its launch stream when

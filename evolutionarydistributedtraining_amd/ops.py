@@ -135,11 +135,8 @@ def delta_stats_list(thetas: list[torch.Tensor], workers: list[list[torch.Tensor
     out = _scratch(dev, int(lib.edt_delta_stats_doubles(K, plan.nchunks)))
     nbytes = lib.edt_delta_stats_list_workspace_bytes(T, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    P_ = ctypes.c_void_p
-    th_arr = (P_ * T)(*[t.data_ptr() for t in thetas])
-    w_arr = (P_ * len(flat_w))(*[t.data_ptr() for t in flat_w])
     numel = (ctypes.c_uint64 * T)(*numels)
-    L.check(lib.edt_delta_stats_list(th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, numel, T,
+    L.check(lib.edt_delta_stats_list(_ptrs(thetas), L.dtype_code(gdt), _ptrs(flat_w), L.dtype_code(wdt), K, numel, T,
                                      L.ptr(plan.chunks), plan.nchunks, L.ptr(out), L.ptr(ws), nbytes,
                                      L.stream_ptr(dev)), "edt_delta_stats_list")
     return out[:plan.nchunks * W].view(plan.nchunks, W)
@@ -207,13 +204,10 @@ def outer_step_list_mix(thetas: list[torch.Tensor], workers: list[list[torch.Ten
     numel = (ctypes.c_uint64 * T)(*numels)
     nbytes = lib.edt_outer_list_mix_workspace_bytes(T, K, nmix)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    P_ = ctypes.c_void_p
-    th_arr = (P_ * T)(*[t.data_ptr() for t in thetas])
-    w_arr = (P_ * len(flat_w))(*[t.data_ptr() for t in flat_w])
-    l_arr = (P_ * len(flat_l))(*[t.data_ptr() for t in flat_l])
-    m_arr = (P_ * T)(*[t.data_ptr() for t in momenta]) if momenta is not None else None
-    L.check(lib.edt_outer_step_list_mix(th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, m_arr, int(has_momentum),
-                                        numel, T, float(lr), float(momentum_coef), int(nesterov), l_arr, nmix, mix,
+    m_arr = _ptrs(momenta) if momenta is not None else None
+    L.check(lib.edt_outer_step_list_mix(_ptrs(thetas), L.dtype_code(gdt), _ptrs(flat_w), L.dtype_code(wdt), K, m_arr,
+                                        int(has_momentum), numel, T, float(lr), float(momentum_coef), int(nesterov),
+                                        _ptrs(flat_l), nmix, mix,
                                         L.ptr(ws), nbytes, L.stream_ptr(dev)), "edt_outer_step_list_mix")
 
 
@@ -221,27 +215,33 @@ def _check_mix_aliasing(thetas, workers, momenta, live, numels) -> None:
     """The mixing step's aliasing rule from data_ptr ranges (what edt_outer_step_list_mix checks
     again on the host side of the ABI): live[j][r] may be exactly workers[j][r]; any other overlap of a
     destination with theta, the momentum, a worker or another destination is refused."""
-    rs = []                                      # (lo, hi, is a destination)
+    rs = []
     for r, n in enumerate(numels):
         if n == 0:
             continue
-        rs.append((thetas[r].data_ptr(), thetas[r].data_ptr() + n * thetas[r].element_size(), False))
-        if momenta is not None:
-            rs.append((momenta[r].data_ptr(), momenta[r].data_ptr() + n * momenta[r].element_size(), False))
-        for l in live:
-            rs.append((l[r].data_ptr(), l[r].data_ptr() + n * l[r].element_size(), True))
-        for k, w in enumerate(workers):
-            if k < len(live) and w[r].data_ptr() == live[k][r].data_ptr():
-                continue                         # the allowed alias: one range
-            rs.append((w[r].data_ptr(), w[r].data_ptr() + n * w[r].element_size(), False))
-    rs.sort(key=lambda x: x[0])
-    end_any = end_live = 0
-    for lo, hi, is_live in rs:
-        if lo < (end_any if is_live else end_live):
-            raise L.EdtError("a merge destination overlaps another operand (only live[j] is workers[j] may alias)")
+        rs += [_byte_range(x[r], False) for x in ((thetas,) if momenta is None else (thetas, momenta))]
+        rs += [_byte_range(l[r], True) for l in live]
+        rs += [_byte_range(w[r], False) for k, w in enumerate(workers)       # but for the allowed alias: one range
+               if not (k < len(live) and w[r].data_ptr() == live[k][r].data_ptr())]
+    _check_writes_disjoint(rs, "a merge destination overlaps another operand (only live[j] is workers[j] may alias)")
+
+
+def _byte_range(t: torch.Tensor, written: bool) -> tuple:
+    return t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), written
+
+
+def _check_writes_disjoint(ranges, message: str) -> None:
+    """The aliasing rule of the list and piece-list entries over (lo, hi, written) byte ranges, as
+    csrc/edt_table.h's Sweep applies it again behind the ABI: a written range may overlap nothing,
+    read ranges may overlap one another, touching and empty ranges overlap nothing. One sort, one
+    pass with the furthest end so far of any range and of a written one."""
+    end_any = end_written = 0
+    for lo, hi, written in sorted(r for r in ranges if r[1] > r[0]):
+        if lo < (end_any if written else end_written):
+            raise L.EdtError(message)
         end_any = max(end_any, hi)
-        if is_live:
-            end_live = max(end_live, hi)
+        if written:
+            end_written = max(end_written, hi)
 
 
 def _check_list_operands(thetas, workers, momenta) -> tuple:
@@ -296,12 +296,9 @@ def _outer_step_list(thetas, workers, momenta, has_momentum, lr, momentum_coef, 
     numel = (ctypes.c_uint64 * T)(*numels)
     nbytes = lib.edt_outer_list_workspace_bytes(T, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=thetas[0].device)
-    P_ = ctypes.c_void_p
-    th_arr = (P_ * T)(*[t.data_ptr() for t in thetas])
-    w_arr = (P_ * len(flat_w))(*[t.data_ptr() for t in flat_w])
-    m_arr = (P_ * T)(*[t.data_ptr() for t in momenta]) if momenta is not None else None
-    head = (th_arr, L.dtype_code(gdt), w_arr, L.dtype_code(wdt), K, m_arr, int(has_momentum), numel, T, float(lr),
-            float(momentum_coef), int(nesterov))
+    m_arr = _ptrs(momenta) if momenta is not None else None
+    head = (_ptrs(thetas), L.dtype_code(gdt), _ptrs(flat_w), L.dtype_code(wdt), K, m_arr, int(has_momentum), numel, T,
+            float(lr), float(momentum_coef), int(nesterov))
     tail = (L.ptr(ws), nbytes, L.stream_ptr(thetas[0].device))
     bits, toff = None, None
     if tails is not None:
@@ -425,15 +422,8 @@ def theta_scatter_mix_list(thetas: list[torch.Tensor], srcs: list[torch.Tensor],
         return
     dev = thetas[0].device
     srcs = _piece_columns("srcs", [srcs], numels, gdt, dev)
-    rs = sorted((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), w)
-                for ts, w in ((srcs, False), (thetas, True), (flat_l if nmix else [], True)) for t in ts if t.numel())
-    end_any = end_written = 0
-    for lo, hi, written in rs:
-        if lo < (end_any if written else end_written):
-            raise L.EdtError("a piece of theta or a merge destination overlaps another operand")
-        end_any = max(end_any, hi)
-        if written:
-            end_written = max(end_written, hi)
+    _check_writes_disjoint([_byte_range(t, w) for ts, w in ((srcs, False), (thetas, True), (flat_l if nmix else [], True))
+                            for t in ts], "a piece of theta or a merge destination overlaps another operand")
     nbytes = lib.edt_theta_scatter_mix_list_workspace_bytes(T, nmix)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     numel = (ctypes.c_uint64 * T)(*numels)
@@ -608,7 +598,8 @@ def q_region_bytes(region_elems: int, fmt) -> int:
     (1 or 1/2 byte per element), then one E8M0 scale byte per 32 elements. Host only."""
     if region_elems < 0 or region_elems % 512:
         raise L.EdtError(f"region_elems {region_elems} is not a multiple of 512")
-    return int(L.load_library().edt_q_region_bytes(int(region_elems), _qfmt(fmt)))
+    _qfmt(fmt)
+    return L.q_packed_bytes(int(region_elems), fmt)
 
 
 ROUNDING = {"nearest": L.EDT_ROUND_NEAREST, "stochastic": L.EDT_ROUND_STOCHASTIC}

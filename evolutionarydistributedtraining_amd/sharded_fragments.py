@@ -61,7 +61,7 @@ import math
 import torch
 
 from . import ops as _ops
-from ._lib import EDT_MAX_WORKERS, EdtError
+from ._lib import EDT_MAX_WORKERS, Q_BITS, EdtError, q_packed_bytes
 from .collectives import Collectives, TorchCollectives
 from .diloco import OuterState, check_sgd_hparams
 from .fragments import FragmentPlan
@@ -71,7 +71,6 @@ from .tracing import traced
 KERNEL_NAMES = ("delta_partial_list", "sgd_sum_list_to", "theta_scatter_mix_list")
 # with a wire format, phases 1 and 2 are these two instead; phase 3 stays theta_scatter_mix_list
 Q_KERNEL_NAMES = ("delta_partial_q_frag", "sgd_sum_q_frag_to", "theta_scatter_mix_list")
-WIRE_BITS = {"mxfp8": 8, "mxfp4": 4}
 
 
 class ShardedFragmentSync:
@@ -82,7 +81,7 @@ class ShardedFragmentSync:
         check_sgd_hparams(lr, momentum, nesterov)
         if plan.layout.numels != layout.numels:
             raise EdtError("the fragment plan does not match the layout")
-        if wire_format is not None and wire_format not in WIRE_BITS:
+        if wire_format is not None and wire_format not in Q_BITS:
             raise EdtError(f"unknown wire format {wire_format!r}: None, 'mxfp8' or 'mxfp4'")
         self.wire_format = wire_format
         self.kernels = kernels or _ops
@@ -150,10 +149,9 @@ class ShardedFragmentSync:
             off += s1 - s0
 
     def _qbytes(self, elems: int) -> int:
-        """Packed bytes of `elems` elements (a multiple of 512) as whole regions: payload + one scale
-        byte per 32 — linear in the elements, so also the byte offset of fragment-space element
+        """q_packed_bytes in this sync's wire format: also the byte offset of fragment-space element
         `elems` in `send` / `recv`."""
-        return elems * WIRE_BITS[self.wire_format] // 8 + elems // 32
+        return q_packed_bytes(elems, self.wire_format)
 
     def _check_fragment(self, p: int) -> None:
         if not 0 <= p < len(self.plan):
@@ -267,7 +265,7 @@ class ShardedFragmentSync:
     def _partial_bytes(self) -> float:
         """Bytes per element of the partial as it is exchanged: 4 (fp32), or the payload plus one
         scale byte per 32 elements."""
-        return 4 if self.wire_format is None else WIRE_BITS[self.wire_format] / 8 + 1 / 32
+        return 4 if self.wire_format is None else q_packed_bytes(512, self.wire_format) / 512
 
     def kernel_bytes(self, p: int, merge: bool = True, mix: float = 1.0) -> int:
         """Algorithmic HBM bytes of the three kernels of one step of fragment p on this rank, steady

@@ -170,7 +170,7 @@ def test_chunk_and_tile_edges(oracle, dev, ops, gdt, wdt, K):
 
 
 # ------------------------------------------------------------------------------------------
-# 2. long lists across the LDS boundary (kListLdsMaxTensors = 8191)
+# 2. long lists across the LDS boundary (kListLdsMaxPieces = 8191)
 
 # 0 twice in a row, 1, 7, 8, 9, one-chunk (2049) and two-chunk (4097) tensors; ~3.4 M elements at T = 8192
 LONG_PATTERN = [0, 1, 7, 8, 9, 2049, 4097, 0, 0, 3, 8, 1, 9, 7, 16]
