@@ -10,12 +10,15 @@ with fused HIP kernels for gfx950 behind the C ABI in include/edt_sync.h (libedt
 from ._lib import EdtError, load_library
 from .diloco import DILOCO_DEFAULTS, DILOCO_SIM_DEFAULTS, OuterState, OuterSync, outer_step, outer_step_fragment
 from .fragments import FragmentPlan
+from .merge import task_merge_models_into_, task_merge_plan, task_merge_state_dicts, task_merge_tensors
+from .ops import task_merge_list
 from .params import ParamArena, ParamLayout, arena_of_module, bind_module_
 from .sharded_fragments import ShardedFragmentSync
 
 __all__ = [
     "EdtError", "load_library", "OuterState", "OuterSync", "outer_step", "DILOCO_DEFAULTS",
     "DILOCO_SIM_DEFAULTS", "ParamArena", "ParamLayout", "arena_of_module", "bind_module_",
-    "FragmentPlan", "outer_step_fragment", "ShardedFragmentSync",
+    "FragmentPlan", "outer_step_fragment", "ShardedFragmentSync", "task_merge_list", "task_merge_tensors",
+    "task_merge_state_dicts", "task_merge_plan", "task_merge_models_into_",
 ]
 __version__ = "0.1.0"

@@ -80,6 +80,11 @@ SIGNATURES = [
     ("edt_theta_scatter_mix_list_workspace_bytes", _U64, [_I, _I]),
     ("edt_theta_scatter_mix_list", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), ctypes.POINTER(_P), _I, _I, _D,
                                         ctypes.POINTER(_U64), _I, _P, _U64, _P]),
+    ("edt_task_merge_list_workspace_bytes", _U64, [_I, _I]),
+    ("edt_task_merge_list", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, _I, ctypes.POINTER(_P), _I,
+                                 ctypes.POINTER(_U64), _I, ctypes.POINTER(ctypes.c_float),
+                                 ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32), _D, _I, _I, _U64, _U64,
+                                 _P, _U64, _P]),
     ("edt_delta_partial_q_frag_workspace_bytes", _U64, [_I, _I]),
     ("edt_delta_partial_q_frag", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), _I, _I, _I, ctypes.POINTER(_U64),
                                       ctypes.POINTER(_U64), _I, _U64, _U64, _U64, _I, _P, _P, _P, _U64, _P]),

@@ -16,12 +16,12 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
-# one shared object from eight translation units (DiLoCo, pair merge + lerp, SLERP, ABI misc, the
+# one shared object from nine translation units (DiLoCo, pair merge + lerp, SLERP, ABI misc, the
 # quantized partial exchange, the pseudo-gradient statistics, the sharded fragment step's piece lists
-# and its quantized phases)
+# and its quantized phases, the task-vector merges)
 SOURCES = [os.path.join(CSRC, f) for f in ("edt_outer.hip", "edt_merge.hip", "edt_slerp.hip", "edt_abi.hip",
                                            "edt_quant.hip", "edt_stats.hip", "edt_fragment.hip",
-                                           "edt_fragment_q.hip")]
+                                           "edt_fragment_q.hip", "edt_taskmerge.hip")]
 HEADER = os.path.join(ROOT, "include", "edt_sync.h")
 DEPS = SOURCES + [HEADER, os.path.join(CSRC, "edt_common.h"), os.path.join(CSRC, "edt_step.h"),
                   os.path.join(CSRC, "edt_chunksum.h"), os.path.join(CSRC, "edt_mx.h"),
@@ -39,7 +39,10 @@ HIPCC_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off
 # member pair with one (edt_slerp.hip, need_dot) — is a plain binary tree of scalar compares and
 # branches instead of the structurizer's flag-variable chain (~40 % fewer instructions in that
 # pass; divergent regions are structured as before).
-TU_FLAGS = {"edt_slerp.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=true"]}
+# edt_taskmerge.hip: no packed fp32 forms on the device (v_pk_add / mul / fma_f32): every operation
+# of its numerics contract is one scalar IEEE fp32 instruction, rounded on its own.
+TU_FLAGS = {"edt_slerp.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=true"],
+            "edt_taskmerge.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hipcc() -> str:

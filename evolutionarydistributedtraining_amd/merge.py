@@ -592,6 +592,159 @@ def merge_models_into_(target: torch.nn.Module, model_1: torch.nn.Module, model_
         target.load_state_dict(slerp_state_dicts(sd1, sd2, plan, out_dtype=out_dtype, device=dev))
 
 
+# ------------------------------------------------------------------------------------------
+# task-vector merges of K models of one base (MergeKit's task_arithmetic / dare_linear / dare_ties)
+
+# merge_method -> (sign consensus, density used)
+TASK_MERGE_METHODS = {"task_arithmetic": (False, False), "dare_linear": (False, True), "dare_ties": (True, True)}
+
+
+def _routed_parameter(name: str, value, default):
+    """A MergeKit parameter that is a scalar or a [{filter, value}] list, as t_for_key's arguments:
+    ({filter: curve}, global value). A filtered scalar is a one-point curve."""
+    if value is None:
+        return {}, default
+    if isinstance(value, numbers.Number):
+        return {}, value
+    if not (isinstance(value, (list, tuple)) and all(isinstance(p, dict) and "value" in p for p in value)):
+        raise EdtError(f"{name}: a scalar or a [{{filter, value}}] list")
+    curves = {p["filter"]: list(p["value"]) if isinstance(p["value"], (list, tuple)) else [p["value"]]
+              for p in value if "filter" in p}
+    return curves, next((p["value"] for p in value if "filter" not in p), default)
+
+
+def task_merge_settings(merge_config_dict: dict) -> dict:
+    """The per-call settings of a task-merge config: consensus (from merge_method), normalize and lam
+    (top-level parameters; MergeKit's defaults, normalize on and lambda 1)."""
+    method = merge_config_dict.get("merge_method")
+    if method not in TASK_MERGE_METHODS:
+        raise EdtError(f"merge_method {method!r}: one of {sorted(TASK_MERGE_METHODS)}")
+    top = merge_config_dict.get("parameters") or {}
+    return {"consensus": TASK_MERGE_METHODS[method][0], "normalize": bool(top.get("normalize", True)),
+            "lam": float(top.get("lambda", 1.0))}
+
+
+def task_merge_plan(keys, num_layers: int, merge_config_dict: dict):
+    """[(key, [weight per model], [density per model])] for the keys a task-merge config covers:
+    every model's `weight` and `density` (a scalar or a [{filter, value}] list, default 1) routed per
+    key exactly as SLERP's t is (t_for_key / interpolate_t: self_attn / mlp curves over the layer
+    index, the unfiltered value elsewhere, keys of layers beyond num_layers skipped). task_arithmetic
+    takes every density as 1. The models are `models`' entries other than `base_model`, in order."""
+    task_merge_settings(merge_config_dict)                  # refuses an unknown merge_method
+    uses_density = TASK_MERGE_METHODS[merge_config_dict["merge_method"]][1]
+    base = merge_config_dict.get("base_model")
+    entries = [m for m in merge_config_dict.get("models", []) if m.get("model") != base or base is None]
+    if not entries:
+        raise EdtError("a task merge needs at least one model besides base_model")
+    routed = []
+    for m in entries:
+        p = m.get("parameters") or {}
+        routed.append((_routed_parameter("weight", p.get("weight"), 1.0),
+                       _routed_parameter("density", p.get("density") if uses_density else None, 1.0)))
+    out = []
+    for k in keys:
+        ws = [t_for_key(k, num_layers, *w) for w, _ in routed]
+        if ws[0] is None:                                   # a layer beyond num_layers: skipped, as SLERP's plan does
+            continue
+        out.append((k, [float(x) for x in ws], [float(t_for_key(k, num_layers, *d)) for _, d in routed]))
+    return out
+
+
+_TASK_PAIRS = {(torch.float32, torch.float32), (torch.float32, torch.bfloat16), (torch.bfloat16, torch.bfloat16)}
+
+
+def task_merge_tensors(bases, models, weights, densities=1.0, *, outs=None, out_dtype=None, device=None, lam=1.0,
+                       consensus=False, normalize=True, seed=0, step=0) -> list[torch.Tensor]:
+    """Task-vector merge of models[k][t] relative to bases[t] in ONE multi-tensor pass
+    (ops.task_merge_list): the merged tensors, on the device, shaped like the bases. weights,
+    densities: a scalar, [K] or [K][T]. Device tensors are read where they lie; anything else (CPU
+    tensors, other dtypes than fp32 / bf16, a base / model dtype pair the kernel lacks: those are
+    widened to fp32) is copied to the device tensor by tensor first. outs: destinations written in
+    place (outs[t] may be bases[t] itself: the in-place form); out_dtype (without outs): fp32 or
+    bf16, default the bases' dtype."""
+    bases = list(bases)
+    models = [list(m) for m in models]
+    if not bases:
+        return []
+    if any(len(m) != len(bases) for m in models):
+        raise EdtError("every model needs one tensor per base tensor")
+    for m in models:
+        for b, x in zip(bases, m):
+            if x.shape != b.shape:
+                raise EdtError(f"a model disagrees with the base on a tensor shape: {tuple(x.shape)} vs {tuple(b.shape)}")
+    dev = device or _compute_device(*bases, *[x for m in models for x in m])
+    gdts, wdts = {b.dtype for b in bases}, {x.dtype for m in models for x in m}
+    gdt, wdt = (next(iter(gdts)), next(iter(wdts))) if len(gdts) == 1 and len(wdts) == 1 else (None, None)
+    if (gdt, wdt) not in _TASK_PAIRS:
+        gdt = wdt = torch.float32
+
+    def resident(x, dt):
+        x = x.detach()
+        return x if x.device == dev and x.dtype == dt and x.is_contiguous() else x.to(device=dev, dtype=dt).contiguous()
+
+    b_dev = [resident(b, gdt) for b in bases]
+    m_dev = [[resident(x, wdt) for x in m] for m in models]
+    if outs is not None:
+        outs = list(outs)
+        if len(outs) != len(bases) or any(o.shape != b.shape for o, b in zip(outs, bases)):
+            raise EdtError("outs must hold one tensor per base tensor, shaped like it")
+        odts = {o.dtype for o in outs}
+        out_dtype = next(iter(odts)) if len(odts) == 1 else torch.float32      # mixed: round once, in copy_
+    elif out_dtype is None:
+        out_dtype = gdt
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        out_dtype = torch.float32
+    direct = outs is not None and all(o.device == dev and o.dtype == out_dtype and o.is_contiguous() for o in outs)
+    res = [o.detach() for o in outs] if direct else [torch.empty(b.shape, dtype=out_dtype, device=dev) for b in bases]
+    ops.task_merge_list(b_dev, m_dev, res, weights=weights, densities=densities, lam=lam, consensus=consensus,
+                        normalize=normalize, seed=seed, step=step)
+    if outs is None:
+        return res
+    if not direct:
+        with torch.no_grad():
+            for o, r in zip(outs, res):
+                o.copy_(r)
+    return outs
+
+
+def task_merge_state_dicts(base_sd: dict, sds, plan, *, out: dict | None = None, out_dtype=None, device=None, lam=1.0,
+                           consensus=False, normalize=True, seed=0, step=0) -> dict:
+    """Merged state dict {key: tensor} for plan = [(key, weights, densities)] (task_merge_plan) of the
+    models' state dicts `sds` relative to base_sd. out: a state dict to write the results into (it may
+    be base_sd itself: in place). CPU tensors go to the device tensor by tensor; there is no arena form."""
+    keys = [k for k, _, _ in plan]
+    K = len(sds)
+    if any(len(w) != K or len(d) != K for _, w, d in plan):
+        raise EdtError("the plan holds one weight and one density per model")
+    weights = [[w[k] for _, w, _ in plan] for k in range(K)]
+    densities = [[d[k] for _, _, d in plan] for k in range(K)]
+    res = task_merge_tensors([base_sd[k] for k in keys], [[sd[k] for k in keys] for sd in sds], weights, densities,
+                             outs=None if out is None else [out[k] for k in keys], out_dtype=out_dtype, device=device,
+                             lam=lam, consensus=consensus, normalize=normalize, seed=seed, step=step)
+    return dict(zip(keys, res))
+
+
+def task_merge_models_into_(target: torch.nn.Module, base_model: torch.nn.Module, models, merge_config_dict: dict,
+                            num_layers: int, seed: int = 0, step: int = 0, device=None) -> None:
+    """The task-vector merge of `models` relative to base_model that merge_config_dict describes
+    (task_merge_plan, task_merge_settings), loaded into `target`: base_model itself (its tensors are
+    rewritten in place, one pass) or another module with the same keys (written where its tensors
+    lie). When the plan skips keys of the target the merged dict goes through load_state_dict, which
+    reports the mismatch. seed / step pick DARE's random bits."""
+    dev = torch.device(device) if device not in (None, "cpu") else None
+    base_sd = module_tensors(base_model)
+    sds = [module_tensors(m) for m in models]
+    plan = task_merge_plan(list(base_sd.keys()), num_layers, merge_config_dict)
+    settings = task_merge_settings(merge_config_dict)
+    tsd = base_sd if target is base_model else module_tensors(target)
+    out_dtype = next(target.parameters()).dtype
+    if set(tsd) == {k for k, _, _ in plan}:
+        task_merge_state_dicts(base_sd, sds, plan, out=tsd, device=dev, seed=seed, step=step, **settings)
+    else:
+        target.load_state_dict(task_merge_state_dicts(base_sd, sds, plan, out_dtype=out_dtype, device=dev, seed=seed,
+                                                      step=step, **settings))
+
+
 def uniform_dna_crossover(dna1, dna2):
     """Per gene, parent 1's value if np.random.rand() > 0.5 else parent 2's, with numpy's global
     RNG (EDT_LM/train/crossover.py:318-321, EDT_RL/crossover.py:167-170)."""

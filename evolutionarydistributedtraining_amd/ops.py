@@ -433,6 +433,93 @@ def theta_scatter_mix_list(thetas: list[torch.Tensor], srcs: list[torch.Tensor],
             "edt_theta_scatter_mix_list")
 
 
+def _per_model_tensor(name: str, v, K: int, T: int) -> np.ndarray:
+    """A scalar, [K] or [K][T] of Python numbers as a float64 [K, T] array."""
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 1 and a.shape == (K,):
+        a = a[:, None]
+    elif a.ndim != 0 and a.shape != (K, T):
+        raise L.EdtError(f"{name}: a scalar, one value per model or one per (model, tensor); got shape {a.shape}")
+    return np.ascontiguousarray(np.broadcast_to(a, (K, T)))
+
+
+def task_merge_coefficients(weights, densities, K: int, T: int) -> tuple:
+    """What `task_merge_list` hands the kernel per (model, tensor), as [K, T] numpy arrays:
+    w = f32(weight); drop16 = clamp(round((1 - density) * 65536), 0, 65535) (uint32; round to nearest,
+    ties to even), the threshold a model's 16 random bits must reach for an element to be kept; and
+    c = f32(w / (1 - drop16 / 65536)) formed in float64, DARE's rescale of the kept entries. A density
+    outside (0, 1] or a weight that is not finite in fp32 is refused. Needs no device."""
+    w64 = _per_model_tensor("weights", weights, K, T)
+    d = _per_model_tensor("densities", densities, K, T)
+    if not np.all((d > 0.0) & (d <= 1.0)):           # NaN fails both comparisons
+        raise L.EdtError("density outside (0, 1]")
+    with np.errstate(over="ignore"):
+        w = w64.astype(np.float32)
+    drop = np.clip(np.rint((1.0 - d) * 65536.0), 0, 65535).astype(np.uint32)
+    with np.errstate(over="ignore"):
+        c = (w.astype(np.float64) / (1.0 - drop.astype(np.float64) / 65536.0)).astype(np.float32)
+    if not (np.all(np.isfinite(w)) and np.all(np.isfinite(c))):
+        raise L.EdtError("weights must be finite in fp32, rescaled by 1 / density too")
+    return w, c, drop
+
+
+def task_merge_list(bases: list[torch.Tensor], models: list[list[torch.Tensor]],
+                    outs: list[torch.Tensor] | None = None, *, weights, densities=1.0, lam: float = 1.0,
+                    consensus: bool = False, normalize: bool = True, seed: int = 0, step: int = 0) -> None:
+    """Task-vector merge of K models relative to a base over T separate tensors in ONE launch
+    (edt_task_merge_list; the contract is in include/edt_sync.h and DESIGN §3): per element, with
+    delta_k = models[k][t] - bases[t] in fp32,
+
+        out = base + lam * elect(sum_k c_k * keep_k * delta_k) / normaliser
+
+    densities 1 and no consensus is MergeKit's `task_arithmetic`, densities below 1 `dare_linear`
+    (each delta kept with probability density by 16 Philox bits of (seed, step, k, element) and
+    rescaled by 1 / density), consensus=True `dare_ties` (the sum is elected among the terms that agree
+    with its sign). weights, densities: a scalar, [K] or [K][T]. outs: fp32 or bf16 tensors (None: in
+    place into bases; outs[t] may be bases[t] itself); any other overlap of an output with an operand
+    is refused: EdtError, nothing launched. bases / models dtypes: fp32 / fp32, fp32 / bf16, bf16 / bf16."""
+    T, K = len(bases), len(models)
+    if K == 0:
+        raise L.EdtError("no models")
+    if K > L.EDT_MAX_WORKERS:
+        raise L.EdtError(f"a task merge takes at most {L.EDT_MAX_WORKERS} models")
+    w, c, drop = task_merge_coefficients(weights, densities, K, T)
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(lam)):
+            raise L.EdtError(f"lam {lam} is not finite in fp32")
+    lib = L.lib()
+    flat_m, numels, gdt, wdt = _check_list_operands(bases, models, None)
+    if T == 0:
+        if outs:
+            raise L.EdtError("outs: one tensor per piece")
+        return
+    dev = bases[0].device
+    odt, o_arr = gdt, None
+    ranges = [_byte_range(t, False) for t in flat_m]
+    if outs is None:
+        ranges += [_byte_range(t, True) for t in bases]
+    else:
+        outs = list(outs)
+        odt = outs[0].dtype if outs else gdt
+        outs = _piece_columns("outs", [outs], numels, odt, dev)
+        for b, o in zip(bases, outs):
+            if o.data_ptr() == b.data_ptr() and odt == gdt:       # the allowed alias: one written range
+                ranges.append(_byte_range(b, True))
+            else:
+                ranges += [_byte_range(b, False), _byte_range(o, True)]
+        o_arr = _ptrs(outs)
+    _check_writes_disjoint(ranges, "an output overlaps another operand (only outs[t] is bases[t] may alias)")
+    nbytes = lib.edt_task_merge_list_workspace_bytes(T, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    numel = (ctypes.c_uint64 * T)(*numels)
+    f32p, u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+    L.check(lib.edt_task_merge_list(_ptrs(bases), L.dtype_code(gdt), _ptrs(flat_m), L.dtype_code(wdt), K, o_arr,
+                                    L.dtype_code(odt), numel, T, w.ctypes.data_as(f32p), c.ctypes.data_as(f32p),
+                                    drop.ctypes.data_as(u32p), float(lam), int(bool(consensus)), int(bool(normalize)),
+                                    int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), L.ptr(ws), nbytes,
+                                    L.stream_ptr(dev)), "edt_task_merge_list")
+
+
 def delta_partial(theta: torch.Tensor, workers: list[torch.Tensor], k_total: int,
                   acc: torch.Tensor, accumulate: bool = False) -> None:
     """acc (fp32) (+)= sum over the local workers of round((theta_k - theta) / k_total)."""

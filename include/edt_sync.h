@@ -390,6 +390,44 @@ int edt_delta_partial_q_sr(const void* theta_g, int gdt, const void* const* thet
 int edt_sgd_apply_sum_q(void* theta_g, int gdt, const void* const* regions, int nacc, int fmt, void* momentum,
                         int has_momentum, uint64_t n, double lr, double momentum_coef, int nesterov, void* stream);
 
+/* ---- task-vector merges of K models relative to a base (task_arithmetic / dare_linear / dare_ties) ----
+ * MergeKit's merges of K fine-tuned models M_0..M_{K-1} (dtype wdt) of one base B (dtype gdt) over T
+ * separate tensors, ONE launch, nothing packed, no temporary (the reference has SLERP only; per-tensor
+ * PyTorch needs K + 1 passes). Per tensor t, element i — all arithmetic fp32, every operation rounded to
+ * nearest on its own, no FMA; bf16 inputs widen exactly:
+ *   delta_k = f32(M_k[i]) - f32(B[i])
+ *   kept_k  = r16(seed, step, stream_id = k, element base_t + i) >= drop16[k][t]     (drop16 == 0 keeps all)
+ *   tau_k   = kept_k ? c[k][t] * delta_k : +0.0f,    c[k][t] = f32(w[k][t] / (1 - drop16[k][t] / 65536)),
+ *             formed by the caller in float64 (DARE's rescale of the kept entries by 1 / density)
+ *   A  = ((tau_0 + tau_1) + ...) in k order;  P = the same sum over the tau_k > 0, N over the tau_k < 0;
+ *   WP / WN = the sums of w[k][t] over those k;  WA = the sum of every w[k][t] (all from +0, in k order)
+ *   consensus:     num = A > 0 ? P : A < 0 ? N : A;   den = A > 0 ? WP : A < 0 ? WN : 1    (A NaN: num = A)
+ *   no consensus:  num = A;  den = WA
+ *   normalize:     den = |den| < 1e-8f ? 1 : den;  q = num / den          (without: q = num)
+ *   out[i] = round_odt(f32(B[i]) + f32(lambda) * q)                      odt fp32, or bf16 to nearest even
+ * r16 is the stochastic-rounding paragraph's above (Philox4x32, EDT_PHILOX_ROUNDS rounds, key = the seed's
+ * two words, counter = (g lo, g hi, step & 0xffffffff, k), g = (base_t + i) / 8; element (base_t + i) % 8
+ * = j takes half j % 2 of word j / 2). base_t is tensor t's offset when the list's sizes are packed with
+ * every start rounded up to a multiple of 8, so the bits depend on the sizes, the seed, the step and k only:
+ * not on addresses, and not on which body (8 elements per lane, or one for tensors off a 16-byte boundary
+ * and for a tensor's last < 8 elements) handles the element. density d <-> drop16 = clamp(round((1 - d) *
+ * 65536), 0, 65535). task_arithmetic: consensus 0, every drop16 0; dare_linear: consensus 0; dare_ties:
+ * consensus 1. With every drop16 == 0 no random bits are computed.
+ *   base_t[T], model_k[K * T] (model-major), numel[T]   host arrays as edt_outer_step_list's
+ *   out_t[T]     host array, dtype odt; NULL: in place into base_t (odt must be gdt). out_t[t] may be
+ *                base_t[t] exactly when odt == gdt; any other overlap of a written range with an operand
+ *                is refused
+ *   w, c, drop16 host arrays [K * T], model-major
+ *   workspace    edt_task_merge_list_workspace_bytes(T, K) bytes of device memory, 8-byte aligned
+ * EDT_ERR_ARG, nothing launched: an invalid dtype pair or odt, K outside [1, EDT_MAX_WORKERS], T < 0, a
+ * null table or a null pointer of a non-empty tensor, a lambda, w or c that is not finite in fp32,
+ * drop16 > 65535, a workspace too small or misaligned, overlapping writes. */
+uint64_t edt_task_merge_list_workspace_bytes(int T, int K);
+int edt_task_merge_list(void* const* base_t, int gdt, const void* const* model_k, int wdt, int K, void* const* out_t,
+                        int odt, const uint64_t* numel, int T, const float* w, const float* c, const uint32_t* drop16,
+                        double lambda, int consensus, int normalize, uint64_t seed, uint64_t step, void* workspace,
+                        uint64_t workspace_bytes, void* stream);
+
 /* ---- the sharded fragment step's quantized phases (Streaming DiLoCo's low-precision outer gradients) ----
  * edt_delta_partial_list / edt_sgd_sum_list_to with the partial crossing the links as MX regions (the
  * wire format above, unchanged) instead of fp32. Both entries work on one FRAGMENT-SPACE RANGE
